@@ -1434,6 +1434,7 @@ static int forward_impl(bde_model* m, const float* const* events, int T, int B, 
 // so the launch sequence can be captured once per (slot, T, B, H, W) into a hipGraph and replayed
 // (~630 launches per forward at config A; replay removes their host cost).
 static int forward_body(bde_model* m, int T, int B, int H, int W, hipStream_t s, int part);
+static bool side_decode_on(const bde_model* m, int T);
 
 static int forward_on(bde_model* m, const float* const* events, int T, int B, int H, int W, float* const* images,
                       hipStream_t s) {
@@ -1454,7 +1455,10 @@ static int forward_on(bde_model* m, const float* const* events, int T, int B, in
     const int part_main = cut ? PART_MAIN : PART_ALL;
     if (guard) BDE_HIP(hipMemsetAsync(m->ovf(), 0, sizeof(unsigned), s));
     if (cut) BDE_TRY(forward_body(m, T, B, H, W, s, PART_PRE));
-    const bool can_graph = m->use_graph && ws.warm;   // (profiling spans are captured as event-record nodes)
+    // (profiling spans are captured as event-record nodes).  A schedule with a forked decode ("overlap") runs eagerly: a second
+    // instantiated graph with a forked branch crashed inside hipGraphLaunch on its first launch, its own side stream and events
+    // notwithstanding, while the first one replayed
+    const bool can_graph = m->use_graph && ws.warm && !side_decode_on(m, T);
     if (ws.graph_exec && ws.graph_part != part_main) { (void)hipGraphExecDestroy(ws.graph_exec); ws.graph_exec = nullptr; }
     if (can_graph && !ws.graph_exec) {
         // capture on a private stream (the caller's may be the legacy default stream, which cannot
@@ -1537,6 +1541,12 @@ static int decode_frames(bde_model* mm, int f0, int nf, int T_, int B_, int H_, 
     return BDE_OK;
 }
 
+static bool side_decode_on(const bde_model* m, int T) {
+    const bde_config& c = m->cfg;
+    const bool plain_flags = c.use_rc && c.recurrent_type == 0 && !c.skip_concat && c.depths[c.num_encoders - 1] > 0;
+    return m->overlap != 0 && plain_flags && !(m->debug_skip & (2 | 8)) && !m->prof_on && T > m->overlap_chunk;
+}
+
 static int forward_body(bde_model* m, int T, int B, int H, int W, hipStream_t s, int part) {
     const bde_config& c = m->cfg;
     Workspace& ws = m->W();
@@ -1546,8 +1556,7 @@ static int forward_body(bde_model* m, int T, int B, int H, int W, hipStream_t s,
     // refined -- independent per frame, V5.py:183-202 -- runs on a side stream in chunks of `overlap_chunk` frames: a forked branch
     // of the captured graph.  The chain's launches are latency-bound and leave most of the chip idle; the decoder's are not.  The
     // last chunk stays on the main stream (it is what the forward's tail is cut from).  Results are bit-identical: same launches.
-    const bool plain_flags = c.use_rc && c.recurrent_type == 0 && !c.skip_concat && c.depths[L - 1] > 0;
-    const bool side_decode = m->overlap != 0 && plain_flags && !(m->debug_skip & (2 | 8)) && !m->prof_on && T > m->overlap_chunk;
+    const bool side_decode = side_decode_on(m, T);
     const int last_chunk_t0 = side_decode ? (T - 1) / m->overlap_chunk * m->overlap_chunk : 0;
     const int tail_f0 = last_chunk_t0 * B, tail_nf = (int)TB - tail_f0;
     if (part == PART_TAIL) return (m->debug_skip & 8) ? BDE_OK : decode_frames(m, tail_f0, tail_nf, T, B, H, W, s, PART_TAIL);

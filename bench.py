@@ -363,6 +363,40 @@ def cpu_baseline(cfg, sd, H, W, T):
                 sample=f'one oracle forward, T={T}, 5x{H}x{W}, torch {torch.__version__} CPU, {dt:.1f} s')
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_voxels(T, sensor_hw, device, seed0, batch, croper):
+    """The grids of workload.bench_voxels (same events, same seeds, same padding) binned on the host in event order
+    (oracle/voxel_oracle.py): bit-identical from run to run, unlike the float atomics of the HIP binning."""
+    import numpy as np
+    import torch
+    from oracle import voxel_oracle
+    sh, sw = sensor_hw
+    grids = np.stack([np.stack([voxel_oracle.events_to_voxel(*voxel_oracle.synthetic_events(sh * sw // 2, sh, sw, seed0 + b * T + t),
+                                                             5, (sh, sw)) for b in range(batch)]) for t in range(T)])
+    return croper.pad(torch.from_numpy(grids)).contiguous().to(device)
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy in float32 for each output.  One larger than DUMP_LIMIT_BYTES in all is replaced by a fixed sample
+    (seed 0, sorted flat indices) stored beside it as DIR/<name>_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes <= budget:
+            np.save(os.path.join(out_dir, name + '.npy'), a)
+            log(f'dumped {name} {list(a.shape)} to {out_dir}')
+            continue
+        k = (budget - 4096) // (4 + 8)                  # (room for the two .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+        np.save(os.path.join(out_dir, name + '.npy'), a.reshape(-1)[idx])
+        np.save(os.path.join(out_dir, name + '_index.npy'), idx.astype(np.float64))
+        log(f'dumped a {k}-element sample of {name} {list(a.shape)} to {out_dir}')
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` without a launcher: start N ranks as CHILD processes (this process has not touched
     the GPU yet) and relay rank 0's JSON line."""
@@ -389,6 +423,10 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-strict', action='store_true', help='skip the strict-fp32 leg (profiling runs: only the default kernels in the trace)')
     ap.add_argument('--pipeline', type=int, default=2, help='independent sequences in flight per GPU (1..4); measured this round on one box: 2 / 3 / 4 in flight = 2296 / 2208 / 2098 frames/s')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the frames of the last timed step to DIR/frames.npy (float32; a seeded '
+                         'sample with its flat indices when larger than 64 MB).  The input grids are then binned on the host in '
+                         'event order, so that they are bit-identical from run to run')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
@@ -436,6 +474,8 @@ def main():
     fixture = workload.find_fixture(T, B, H, W, [args.height, args.width])
     seed0 = fixture[1]['seed'] if fixture else workload.SEED0
     vox, n_events, vox_dt = workload.bench_voxels(T, (args.height, args.width), device, seed0=seed0, batch=B)
+    if args.dump_outputs:
+        vox = host_voxels(T, (args.height, args.width), device, seed0, B, croper)
     inputs = [{'events': vox[t]} for t in range(T)]
     log(f'voxel grids ready ({n_events} events in {vox_dt*1e3:.1f} ms)')
     can_verify = fixture is not None
@@ -468,6 +508,8 @@ def main():
         elapsed = time.perf_counter() - t0
         if model.get_info('debug_skip') != 0:
             raise SystemExit('debug_skip was set during the timed region')
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'frames': torch.stack(last)})
         # ---- the frames of the last timed step against the reference's ------------------------------
         verified, verr = None, None
         if can_verify:

@@ -641,8 +641,8 @@ def test_forked_decoder_is_bit_identical_to_the_serial_schedule():
     the frames already refined runs in chunks of four on a forked branch of the captured graph beside the last level's attention
     chain (V5.py:183-202 is independent per frame); the last chunk and the cut
     into eager head / graph / eager tail around the range guard's read-back are part of the same schedule.  Every launch is the
-    launch of the serial schedule restricted to its frames: frames equal bit for bit, eager, captured and replayed, one sequence
-    in flight or three."""
+    launch of the serial schedule restricted to its frames: frames equal bit for bit, call after call, one sequence in flight or
+    three (a forked schedule runs eagerly: csrc/api_schedule.h, forward_on)."""
     from tests.util import golden_inputs
     from bde2vid_amd import canonical
     from bde2vid_amd.model import build_model
@@ -657,7 +657,7 @@ def test_forked_decoder_is_bit_identical_to_the_serial_schedule():
             ref = torch.stack(m(inp)).clone()
             ref2 = torch.stack(m(inp)).clone()            # second call of the shape: the captured graph
             m.set_tuning('overlap', 1)
-            outs = [torch.stack(m(inp)).clone() for _ in range(3)]   # eager, capture, replay
+            outs = [torch.stack(m(inp)).clone() for _ in range(3)]
             m.set_tuning('pipeline', 3)
             pip = [m(inp) for _ in range(7)]
             m.wait()
