@@ -57,14 +57,14 @@ struct Arena {
 struct AttnBlock {
     PackedLayer qkv, proj, fc1, fc2;
     long proj16 = -1, fc1_16 = -1, fc2_16 = -1, qkv16 = -1;   // 16x16x4 packings for token_fused.h
-    long projW = -1, fc1W = -1, fc2W = -1, qkvW = -1;         // four-k-steps-per-load packings for wideblock.h
+    long projW = -1, fc1W = -1, fc2W = -1, qkvW = -1;         // four-k-steps-per-load packings for the fp32 wide chain (tokgemm_kernel,
+                                                              // attn_tok16_kernel)
     long projS = -1, fc1S = -1, fc2S = -1, qkvS = -1;         // split packings for winblock_sb.h, three bf16 terms
     long projH = -1, fc1H = -1, fc2H = -1, qkvH = -1;         // two fp16 terms; unscaleH -> {q|k|v, proj, fc1, fc2} inverse scales
     long unscaleH = -1;                                       // (four floats in the packed image)
-    long qkvHF = -1, qkvHF_unscale = -1;                      // q|k|v as two fp16 terms in FRAG16 k order (attn_tok16_kernel<true, true>)
-    long projHF = -1, fc1HF = -1, mlpHF_unscale = -1;         // proj, fc1 likewise (projfc1_sb_kernel); unscale: {proj, fc1}
+    long projHF = -1, projHF_unscale = -1;                    // proj as two fp16 terms in FRAG16 k order (mlp_fused_kernel)
     long fc1N = -1, fc2N = -1, mlpN_unscale = -1;             // fc1, fc2 as two fp16 terms in natural k order (mlp_fused_kernel); unscale: {fc1, fc2}
-    long qkvN = -1, qkvN_unscale = -1;                        // q|k|v likewise (wide_core_kernel on SPL16 operands)
+    long qkvN = -1, qkvN_unscale = -1;                        // q|k|v likewise (wide_core_kernel)
     long kvpad_off = -1;    // [2C]
     long bias_off = -1;     // [heads][D*49][49]
     long biasF_off = -1;    // the same bias in the score-tile order of winblock.h (64 channels, 16 heads only)
@@ -74,8 +74,8 @@ struct AttnLevel {
     int depth = 0, C = 0;
     std::vector<AttnBlock> blocks;
     PackedLayer kvall;      // rows = depth*2C: K|V of every block for a non-query frame
-    long kvallW = -1;       // the same rows packed for wideblock.h
-    long kvallH = -1, kvallH_unscale = -1;   // ... and as two fp16 terms for tokgemm_sb_kernel (k order of FRAG16 group pairs)
+    long kvallW = -1;       // the same rows packed for the fp32 wide chain (tokgemm_kernel)
+    long kvallH = -1, kvallH_unscale = -1;   // ... and as two fp16 terms for the split chain (tokgemm_sb_*kernel, k order of FRAG16 group pairs)
 };
 
 struct Workspace {
@@ -182,8 +182,6 @@ struct bde_model {
     int winblock = 1;             // one launch per attention block (winblock.h) where the level qualifies
     int winblock_sb = 1;          // ... with its GEMM phases on the bf16 matrix cores, three-term split operands (winblock_sb.h)
     int fuse_pred = 1;            // predI + sigmoid in the last decoder conv's epilogue
-    int wide = 1;                 // head_dim-16 attention levels on the fragment-layout chain (wideblock.h)
-    int wide_fuse_qkv = 1;        // ... with the query frame's q | k | v computed inside the attention core (no GEMM launch of its own)
     int xcd_remap = 1;            // conv_sb workgroup order by XCD (conv_sb.h)
     int head3 = 1;                // head convolution on the three-columns-per-chunk image (conv_sb.h, KS_HEAD3): 10 MFMA taps instead of 25
     int fuse_enc_sb = 1;          // encoder conv epilogue writes the SB16 input of its gate conv (no fp32 planes, no conversion pass)
@@ -195,14 +193,12 @@ struct bde_model {
     hipStream_t dir_stream[4] = {};         // per workspace slot: the second direction's stream and its fork / join events
     hipEvent_t dir_fork[4] = {}, dir_join[4] = {};
     int use_lstm_sbk = 1;         // recurrent step on the 16-bit matrix cores with the pointwise tail fused (lstm_sb.h) where a shape fits
-    int wide_fuse_mlp = 1;        // ... and x1 = x + proj(.) together with GELU(fc1(LN(x1))) in one launch (projfc1_sb_kernel)
-    int wide_fuse_fc2 = 1;        // ... and fc2 + both residuals in the same launch (mlp_fused_kernel, wide_mlp.h): two launches per block
-    int wide_prefetch = 0;        // 1: the attention core warms the L2s with the weights of the MLP launch behind it (wide_core.h).  Measured:
-                                  // the MLP launch's first phase 13.2 k -> 12.5 k cycles, the bench 2191 -> 2124 / 1790 -> 1779 frames/s: off
-    int wide_spl = 1;             // ... on frames kept as SPL16 (pre-split operand fragments + LayerNorm statistics, wide_core.h)
-    int wide_core2 = 1;           // the window half of such a block as wide_core_kernel (wide_core.h): weights by LDS-DMA, K | V of the
-                                  // refined neighbour frame computed inside (no K|V GEMM launch between two frames)
-    int wide_kv_sb = 1;           // K|V GEMMs of the head_dim-16 chain on two-term split operands (tokgemm_sb_kernel, wideblock.h)
+    // Head_dim-16 attention levels (the wide chain, wideblock.h) run one of two chains; the two switches below are ONE choice, kept
+    // as two keys for callers that set them (either at 0 selects the fp32 chain).  Split chain (both 1, sb_terms = 2, C = 256):
+    // K|V on two-term operands (tokgemm_sb_rows_kernel), per block wide_core_kernel + mlp_fused_kernel on SPL16 frames.
+    // fp32 chain: K|V by tokgemm_kernel, per block attn_tok16_kernel + three tokgemm_kernel launches.  (split_chain_ok)
+    int wide_kv_sb = 1;
+    int wide_fuse_mlp = 1;
     int lstm_fuse_x = 1;          // ... and the x-part of the gates in the same contraction (no batched gate convolution, no gx round trip)
     int lstm_sb_mode = 0;         // recurrent step as conv_sb + pointwise kernel: 0 off (default: measured slower), 1 wherever it fits, -1 by estimate
     long fused_min_tiles = 160;   // token_fused.h is used when a level has at least this many 32-pixel tiles

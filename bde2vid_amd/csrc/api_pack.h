@@ -657,15 +657,14 @@ static int build_packed(bde_model* m) {
             fc2.bias.assign(b2b, b2b + C);
             ab.fc2 = pack_layer(ar, {&fc2}, false);
             if (C % 64 == 0 && hd == 16) {
+                // the wide chain (wideblock.h): fp32 chain -- tokgemm_kernel (proj, fc1, fc2), attn_tok16_kernel (q|k|v)
                 ab.projW = pack16x4(ar, proj.w.data(), C, C);
                 ab.fc1W = pack16x4(ar, fc1.w.data(), hid, C);
                 ab.fc2W = pack16x4(ar, fc2.w.data(), C, hid);
                 ab.qkvW = pack16x4(ar, qkv.w.data(), 3 * C, C);
-                ab.qkvHF_unscale = ar.alloc(4);
-                ab.qkvHF = pack16_split_frag(ar, qkv.w.data(), 3 * C, C, ab.qkvHF_unscale);
-                ab.mlpHF_unscale = ar.alloc(4);
-                ab.projHF = pack16_split_frag(ar, proj.w.data(), C, C, ab.mlpHF_unscale);
-                ab.fc1HF = pack16_split_frag(ar, fc1.w.data(), hid, C, ab.mlpHF_unscale + 1);
+                // split chain -- mlp_fused_kernel (proj, fc1, fc2), wide_core_kernel (q|k|v)
+                ab.projHF_unscale = ar.alloc(4);
+                ab.projHF = pack16_split_frag(ar, proj.w.data(), C, C, ab.projHF_unscale);
                 ab.mlpN_unscale = ar.alloc(4);
                 ab.fc1N = pack16_split(ar, fc1.w.data(), hid, C, 2, ab.mlpN_unscale);
                 ab.fc2N = pack16_split(ar, fc2.w.data(), C, hid, 2, ab.mlpN_unscale + 1);

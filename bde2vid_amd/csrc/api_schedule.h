@@ -202,7 +202,7 @@ static int ws_alloc(Workspace& ws, float** p, long numel) {
 
 static bool winblock_ok(const bde_model* m, int l);
 static bool wide_ok(const bde_model* m, int l);
-static bool wide_core2_ok(const bde_model* m, int l);
+static bool split_chain_ok(const bde_model* m, int l);
 static bool lstm_sb_ok(const bde_model* m, int l, int B, int h, int w);
 static bool lstm_sbk_ok(const bde_model* m, int l, int h, int w);
 static bool lstm_sbx_ok(const bde_model* m, int l, int h, int w);
@@ -252,15 +252,14 @@ static int ensure_workspace(bde_model* m, int T, int B, int H, int W) {
                 // (the K|V stacks of the split path are 71 GB at 1280x720, T = 64)
                 BDE_TRY(ws_alloc(ws, &ws.mergedT[l], TB * C * hw));
             } else if (wide_ok(m, l)) {
-                // fragment-layout twin of merged (token tiles of 16) + token-major K|V stacks and first-block q|k|v
+                // fragment-layout twin of merged (token tiles of 16) + token-major K|V stacks
                 BDE_TRY(ws_alloc(ws, &ws.mergedT[l], TB * C * hwp));
-                if (wide_core2_ok(m, l)) {                    // ... and its SPL16 twin + statistics (wide_core.h)
+                if (split_chain_ok(m, l)) {                    // ... and its SPL16 twin + statistics (wide_core.h)
                     BDE_TRY(ws_alloc(ws, &ws.mergedS[l], TB * C * hwp));
                     BDE_TRY(ws_alloc(ws, &ws.mstats[l], TB * hwp * 2));
                 }
                 BDE_TRY(ws_alloc(ws, &ws.kvun[l], TB * c.depths[l] * 2 * C * hw));
                 BDE_TRY(ws_alloc(ws, &ws.kvref[l], TB * c.depths[l] * 2 * C * hw));
-                BDE_TRY(ws_alloc(ws, &ws.qkv0[l], TB * 3 * C * hw));
             } else {
                 BDE_TRY(ws_alloc(ws, &ws.kvun[l], TB * c.depths[l] * 2 * C * hw));
                 BDE_TRY(ws_alloc(ws, &ws.kvref[l], TB * c.depths[l] * 2 * C * hw));
@@ -766,8 +765,7 @@ static int run_attention_frame(bde_model* m, int l, const float* xq, const float
         a.pt = pt; a.pl = plft; a.nWw = Wp / 7; a.dilated = dil ? 1 : 0;
         {
             ProfScope ps(m, pname("chain_core", l), s);
-            if (C / c.num_heads == 16 && D * ATT_TOK <= 160 && tuning().attn_mfma) BDE_TRY(attn_mfma16_launch(a, B, s));
-            else BDE_TRY(attn_launch(a, B, s));
+            BDE_TRY(attn_launch(a, B, s));
         }
         float* dst = last ? out : (x == ws.xa ? ws.xb : ws.xa);
         if (fused) {
@@ -875,21 +873,33 @@ static int run_attention_frame_win(bde_model* m, int l, const float* const* fram
 
 static bool wide_ok(const bde_model* m, int l) {
     const AttnLevel& al = m->attn[l];
-    return m->wide && al.depth > 0 && !winblock_ok(m, l) && al.kvallW >= 0 && al.blocks[0].qkvW >= 0 &&
+    return al.depth > 0 && !winblock_ok(m, l) && al.kvallW >= 0 && al.blocks[0].qkvW >= 0 &&
            m->cfg.frame_num * ATT_TOK <= 160;
+}
+
+// The split chain of a wide level (wideblock.h, wide_core.h, wide_mlp.h; bde_model::wide_kv_sb): two-term operands, C = 256,
+// head_dim 16, every pack present.  Otherwise a wide level runs the fp32 chain.
+static bool split_chain_ok(const bde_model* m, int l) {
+    const AttnLevel& al = m->attn[l];
+    if (!(m->wide_kv_sb && m->wide_fuse_mlp && m->sb_terms == 2 && al.C == 256 && m->cfg.num_heads * 16 == al.C && al.depth > 0 &&
+          al.kvallH >= 0))
+        return false;
+    for (const AttnBlock& ab : al.blocks)
+        if (ab.biasW_off < 0 || ab.qkvN < 0 || ab.projHF < 0 || ab.fc1N < 0 || ab.fc2N < 0 || ab.fc1.Cout != 4 * al.C) return false;
+    return true;
 }
 
 // One GEMM of the wide chain (wideblock.h): x FRAG16 [B][ntile][K/16][256] -> token-major or FRAG16
 static int run_tokgemm(bde_model* m, const char* span, int l, long w_off, const PackedLayer& pl, int M, int K, const float* x, int B,
                        long HW, float* out_tok, float* out_frag, int act, const float* res, const float* addres, float* out_nchw,
-                       int mask_w, int mask_pt, int mask_pl, long row_off, hipStream_t s, long wH_off = -1, long wH_unscale = -1) {
+                       int mask_w, int mask_pt, int mask_pl, hipStream_t s, long wH_off = -1, long wH_unscale = -1) {
     TokGemmArgs a;
     memset(&a, 0, sizeof a);
     const int ntile = (int)cdivl(HW, 16);
     a.x = x;
-    a.w = m->P(w_off) + row_off / 16 * (K / 16) * 256;
-    a.bias = m->P(pl.b_off) + row_off;
-    a.lnsum = pl.s_off >= 0 ? m->P(pl.s_off) + row_off : nullptr;
+    a.w = m->P(w_off);
+    a.bias = m->P(pl.b_off);
+    a.lnsum = pl.s_off >= 0 ? m->P(pl.s_off) : nullptr;
     a.out_tok = out_tok;
     a.out_frag = out_frag;
     a.out_nchw = out_nchw;
@@ -903,7 +913,7 @@ static int run_tokgemm(bde_model* m, const char* span, int l, long w_off, const 
     a.act = act;
     a.mask_w = mask_w; a.mask_pt = mask_pt; a.mask_pl = mask_pl;
     ProfScope ps(m, pname(span, l), s);
-    if (wH_off >= 0 && m->wide_kv_sb && m->sb_terms == 2 && row_off == 0) {      // two fp16 terms on the matrix cores (tokgemm_sb_kernel)
+    if (wH_off >= 0 && split_chain_ok(m, l)) {          // the split chain's K|V: two fp16 terms on the matrix cores (tokgemm_sb_*kernel)
         a.wS = reinterpret_cast<const unsigned short*>(m->P(wH_off));
         a.w_unscale = m->P(wH_unscale);
         a.ovf = m->ovf();
@@ -916,17 +926,12 @@ static int run_tokgemm(bde_model* m, const char* span, int l, long w_off, const 
 //   xq       : query frame, FRAG16 [B][ntile][C/16][256]
 //   kvslot[d]: token-major K|V stack [B][HW][depth*2C] of slot d's frame (nullptr = zero frame; ignored for q_idx)
 //   addres   : FRAG16 tensor added to the result (merged[t]) or nullptr;   out: FRAG16;   out_nchw: optional [B][C][HW]
-//   qkv_first: token-major q|k|v [B][HW][3C] of block blk0 for xq if already computed (batched over T)
 //   prev_frag / prev_slot: FRAG16 frame of ONE refined neighbour (buffer slot prev_slot) whose K | V the attention core computes
-//              itself (wide_core.h) instead of reading kvslot[prev_slot]; nullptr = none
-static bool wide_core2_ok(const bde_model* m, int l) {
-    const AttnLevel& al = m->attn[l];
-    return m->wide_core2 && m->wide_fuse_qkv && m->wide_kv_sb && m->sb_terms == 2 && al.C == 256 && m->cfg.num_heads * 16 == al.C &&
-           al.depth > 0 && al.blocks[0].biasW_off >= 0 && al.blocks[0].qkvHF >= 0;
-}
+//              itself (wide_core.h) instead of reading kvslot[prev_slot]; nullptr = none (split chain only)
+//   xq_twin / prev_twin: SPL16 twins of xq / prev_frag; out_twin: where the last block writes the twin of out (split chain only)
 struct WideTwin { float* s = nullptr; float* st = nullptr; };     // SPL16 image (as float*) and statistics of a FRAG16 frame, or nothing
 static int run_attention_frame_wide(bde_model* m, int l, const float* xq, const float* const* kvslot, const float* addres, float* out,
-                                    float* out_nchw, int B, int H, int W, int blk0, int nblk, const float* qkv_first, hipStream_t s,
+                                    float* out_nchw, int B, int H, int W, int blk0, int nblk, hipStream_t s,
                                     const float* prev_frag = nullptr, int prev_slot = -1, WideTwin xq_twin = WideTwin(),
                                     WideTwin out_twin = WideTwin(), WideTwin prev_twin = WideTwin()) {
     const bde_config& c = m->cfg;
@@ -938,19 +943,17 @@ static int run_attention_frame_wide(bde_model* m, int l, const float* xq, const 
     const int pt = ph / 2, plft = pw / 2;
     const int ntile = (int)cdivl(HW, 16);
     const float* x = xq;
-    WideTwin xt = xq_twin;
-    // SPL16 operands for the core: every frame it reads has its twin, and every block that produces a frame writes one (mlp_fused_kernel)
-    const bool will_fuse_mlp = m->wide_fuse_mlp && m->wide_fuse_fc2 && m->sb_terms == 2 && C == 256 && ws.tile_count && ws.xaS;
-    const bool spl = m->wide_spl && wide_core2_ok(m, l) && will_fuse_mlp && xq_twin.s && (!prev_frag || prev_twin.s) && al.blocks[0].qkvN >= 0;
-    for (int i = blk0; i < blk0 + nblk; ++i) {
-        const AttnBlock& ab = al.blocks[i];
-        const bool dil = (i % 2) == 1;                       // DTransformer.py:362
-        const bool last = (i == blk0 + nblk - 1);
-        if (wide_core2_ok(m, l)) {
+    if (split_chain_ok(m, l)) {
+        // split chain: every frame the core reads has its SPL16 twin, and every block writes the twin of its output (mlp_fused_kernel)
+        BDE_REQUIRE(xq_twin.s && out_twin.s && (!prev_frag || prev_twin.s) && ws.tile_count,
+                    "wide split chain: SPL16 twins of the frames are missing");
+        WideTwin xt = xq_twin;
+        for (int i = blk0; i < blk0 + nblk; ++i) {
+            const AttnBlock& ab = al.blocks[i];
+            const bool dil = (i % 2) == 1;                   // DTransformer.py:362
+            const bool last = (i == blk0 + nblk - 1);
             WideCoreArgs a;
             memset(&a, 0, sizeof a);
-            a.x = x;
-            a.xp = prev_frag;
             a.x_bs = (long)ntile * 16 * C;
             a.q_slot = c.q_idx;
             a.p_slot = prev_frag ? prev_slot : -1;
@@ -962,89 +965,32 @@ static int run_attention_frame_wide(bde_model* m, int l, const float* xq, const 
             }
             a.kvpad = m->P(ab.kvpad_off);
             a.biasW = m->P(ab.biasW_off);
-            a.wqkvS = reinterpret_cast<const unsigned short*>(m->P(spl ? ab.qkvN : ab.qkvHF));
-            a.wqkv_unscale = m->P(spl ? ab.qkvN_unscale : ab.qkvHF_unscale);
-            if (spl) {
-                a.xS = reinterpret_cast<const unsigned short*>(xt.s);
-                a.xSt = xt.st;
-                a.xpS = prev_frag ? reinterpret_cast<const unsigned short*>(prev_twin.s) : nullptr;
-                a.xpSt = prev_frag ? prev_twin.st : nullptr;
-                a.spl_bs = (long)ntile * 16 * C * 2;          // 16-bit elements: two terms per value
-                a.st_bs = (long)ntile * 16 * 2;
-                a.zeros = m->P(m->zero_off);
-            }
+            a.wqkvS = reinterpret_cast<const unsigned short*>(m->P(ab.qkvN));
+            a.wqkv_unscale = m->P(ab.qkvN_unscale);
+            a.xS = reinterpret_cast<const unsigned short*>(xt.s);
+            a.xSt = xt.st;
+            a.xpS = prev_frag ? reinterpret_cast<const unsigned short*>(prev_twin.s) : nullptr;
+            a.xpSt = prev_frag ? prev_twin.st : nullptr;
+            a.spl_bs = (long)ntile * 16 * C * 2;             // 16-bit elements: two terms per value
+            a.st_bs = (long)ntile * 16 * 2;
+            a.zeros = m->P(m->zero_off);
             a.bqkv = m->P(ab.qkv.b_off);
             a.sqkv = m->P(ab.qkv.s_off);
             a.out = ws.ao;
             a.D = D; a.C = C; a.heads = c.num_heads; a.H = H; a.W = W; a.Hp = H + ph; a.Wp = W + pw;
             a.pt = pt; a.pl = plft; a.nWw = (W + pw) / 7; a.dilated = dil ? 1 : 0; a.ntile = ntile;
-            a.ovf = m->ovf();
-            if (m->wide_prefetch && will_fuse_mlp && ab.projHF >= 0 && ab.fc1N >= 0) {
-                a.pf_ptr[0] = reinterpret_cast<const unsigned char*>(m->P(ab.projHF));   // proj, two terms: 4 bytes per weight
-                a.pf_bytes[0] = 4L * C * C;
-                a.pf_ptr[1] = reinterpret_cast<const unsigned char*>(m->P(ab.fc1N));
-                a.pf_bytes[1] = 4L * 4 * C * C;
-            }
             a.stamps = m->tok_debug == 22 ? m->tok_stamps : nullptr;
-            ProfScope ps(m, pname("wide_core", l), s);
-            BDE_TRY(wide_core_launch(a, B, s));
-        } else {
-        BDE_REQUIRE(prev_frag == nullptr, "wide chain: K | V of the refined frame are expected from the attention core");
-        const float* qkv = ws.qkv;
-        const bool fuse_qkv = m->wide_fuse_qkv != 0;       // q | k | v of the query frame inside the attention core (wideblock.h)
-        if (fuse_qkv) qkv = nullptr;
-        else if (i == blk0 && qkv_first) qkv = qkv_first;
-        else BDE_TRY(run_tokgemm(m, "wide_qkv", l, ab.qkvW, ab.qkv, 3 * C, C, x, B, HW, ws.qkv, nullptr, ACT_NONE, nullptr, nullptr,
-                                 nullptr, 0, 0, 0, 0, s));
-        AttnTokArgs a;
-        memset(&a, 0, sizeof a);
-        if (fuse_qkv) {
-            a.x = x;
-            a.x_bs = (long)ntile * 16 * C;
-            a.wqkv = m->P(ab.qkvW);
-            a.bqkv = m->P(ab.qkv.b_off);
-            a.sqkv = m->P(ab.qkv.s_off);
-            a.q_slot = c.q_idx;
-            if (m->wide_kv_sb && m->sb_terms == 2 && ab.qkvHF >= 0) {          // q|k|v on two fp16 terms (wideblock.h)
-                a.wqkvS = reinterpret_cast<const unsigned short*>(m->P(ab.qkvHF));
-                a.wqkv_unscale = m->P(ab.qkvHF_unscale);
-                a.ovf = m->ovf();
-            }
-        }
-        a.q = qkv;
-        a.q_bs = HW * 3 * C;
-        a.q_ld = 3 * C;
-        for (int d = 0; d < D; ++d) {
-            if (d == c.q_idx) {
-                a.kv[d] = qkv; a.kv_bs[d] = HW * 3 * C; a.kv_ld[d] = 3 * C; a.k_off[d] = C; a.v_off[d] = 2 * C;
-            } else if (kvslot[d]) {
-                a.kv[d] = kvslot[d]; a.kv_bs[d] = HW * al.depth * 2 * C; a.kv_ld[d] = al.depth * 2 * C;
-                a.k_off[d] = i * 2 * C; a.v_off[d] = i * 2 * C + C;
-            } else {
-                a.kv[d] = nullptr;
-            }
-        }
-        a.kvpad = m->P(ab.kvpad_off);
-        a.biasT = m->P(ab.bias_off);
-        a.out = ws.ao;
-        a.out_bs = (long)ntile * 16 * C;
-        a.D = D; a.C = C; a.heads = c.num_heads; a.H = H; a.W = W; a.Hp = H + ph; a.Wp = W + pw;
-        a.pt = pt; a.pl = plft; a.nWw = (W + pw) / 7; a.dilated = dil ? 1 : 0; a.ntile = ntile;
-        { ProfScope ps(m, pname("wide_core", l), s); BDE_TRY(attn_tok16_launch(a, B, s)); }
-        }
-        float* dst = (last && out) ? out : (x == ws.xa ? ws.xb : ws.xa);     // out == nullptr: the caller only wants out_nchw
-        // x1 = shortcut + proj(attn)   (uncovered pixels of a dilated block: shortcut only; DTransformer.py:299, 79-82)
-        // hidden = GELU(fc1(LN(x1))): with two-term operands both in one launch (projfc1_sb_kernel)
-        if (m->wide_fuse_mlp && m->wide_fuse_fc2 && m->sb_terms == 2 && ab.projHF >= 0 && ab.fc1N >= 0 && C == 256 && ab.fc1.Cout == 4 * C &&
-            ws.tile_count) {
-            // the whole token half of the block in one launch (wide_mlp.h)
+            { ProfScope ps(m, pname("wide_core", l), s); BDE_TRY(wide_core_launch(a, B, s)); }
+            // x2 = x1 + fc2(GELU(fc1(LN(x1)))), x1 = shortcut + proj(attn): the whole token half of the block in one launch (wide_mlp.h)
+            float* dst = (last && out) ? out : (x == ws.xa ? ws.xb : ws.xa);     // out == nullptr: the caller only wants out_nchw
+            const WideTwin dt = last ? out_twin : (dst == ws.xa ? WideTwin{ws.xaS, ws.stA} : WideTwin{ws.xbS, ws.stB});
             MlpFusedArgs fa;
             memset(&fa, 0, sizeof fa);
             fa.ao = ws.ao; fa.x = x;
             fa.wprojS = reinterpret_cast<const unsigned short*>(m->P(ab.projHF));
             fa.wfc1S = reinterpret_cast<const unsigned short*>(m->P(ab.fc1N));
             fa.wfc2S = reinterpret_cast<const unsigned short*>(m->P(ab.fc2N));
-            fa.unscale_proj = m->P(ab.mlpHF_unscale);
+            fa.unscale_proj = m->P(ab.projHF_unscale);
             fa.unscale_mlp = m->P(ab.mlpN_unscale);
             fa.bproj = m->P(ab.proj.b_off);
             fa.bfc1 = m->P(ab.fc1.b_off);
@@ -1060,47 +1006,53 @@ static int run_attention_frame_wide(bde_model* m, int l, const float* xq, const 
             fa.HW = (int)HW; fa.ntile = ntile; fa.B = B;
             fa.mask_w = dil ? W : 0; fa.mask_pt = pt; fa.mask_pl = plft;
             fa.ovf = m->ovf();
-            if (spl) {
-                const WideTwin dt = last ? out_twin : (dst == ws.xa ? WideTwin{ws.xaS, ws.stA} : WideTwin{ws.xbS, ws.stB});
-                fa.out_spl = reinterpret_cast<unsigned short*>(dt.s);
-                fa.out_stats = dt.st;
-                fa.spl_bs = (long)ntile * 16 * C * 2;
-                fa.st_bs = (long)ntile * 16 * 2;
-                xt = dt;
-            }
+            fa.out_spl = reinterpret_cast<unsigned short*>(dt.s);
+            fa.out_stats = dt.st;
+            fa.spl_bs = (long)ntile * 16 * C * 2;
+            fa.st_bs = (long)ntile * 16 * 2;
             fa.stamps = m->tok_debug == 21 ? m->tok_stamps : nullptr;
-            ProfScope ps(m, pname("wide_mlp", l), s);
-            BDE_TRY(mlp_fused_launch(fa, s));
+            { ProfScope ps(m, pname("wide_mlp", l), s); BDE_TRY(mlp_fused_launch(fa, s)); }
             x = dst;
-            continue;
+            xt = dt;
         }
-        if (m->wide_fuse_mlp && m->sb_terms == 2 && ab.projHF >= 0 && C == 256 && ab.fc1.Cout == 4 * C) {
-            ProjFc1Args pa;
-            memset(&pa, 0, sizeof pa);
-            pa.ao = ws.ao; pa.x = x; pa.x1 = ws.x1; pa.hid = ws.hid;
-            pa.wprojS = reinterpret_cast<const unsigned short*>(m->P(ab.projHF));
-            pa.wfc1S = reinterpret_cast<const unsigned short*>(m->P(ab.fc1HF));
-            pa.proj_unscale = m->P(ab.mlpHF_unscale);
-            pa.fc1_unscale = m->P(ab.mlpHF_unscale + 1);
-            pa.bproj = m->P(ab.proj.b_off);
-            pa.bfc1 = m->P(ab.fc1.b_off);
-            pa.sfc1 = m->P(ab.fc1.s_off);
-            pa.x_bs = (long)ntile * 16 * C;
-            pa.hid_bs = (long)ntile * 16 * 4 * C;
-            pa.C = C; pa.hidden = 4 * C; pa.HW = (int)HW; pa.ntile = ntile;
-            pa.mask_w = dil ? W : 0; pa.mask_pt = pt; pa.mask_pl = plft;
-            pa.ovf = m->ovf();
-            ProfScope ps(m, pname("wide_projfc", l), s);
-            BDE_TRY(projfc1_sb_launch(pa, B, s));
-        } else {
+        return BDE_OK;
+    }
+    // fp32 chain
+    BDE_REQUIRE(prev_frag == nullptr, "wide fp32 chain: K | V of the refined frame are expected in kvslot");
+    for (int i = blk0; i < blk0 + nblk; ++i) {
+        const AttnBlock& ab = al.blocks[i];
+        const bool dil = (i % 2) == 1;                       // DTransformer.py:362
+        const bool last = (i == blk0 + nblk - 1);
+        AttnTokArgs a;
+        memset(&a, 0, sizeof a);
+        a.x = x;                                             // q | k | v of the query frame inside the attention core (wideblock.h)
+        a.x_bs = (long)ntile * 16 * C;
+        a.wqkv = m->P(ab.qkvW);
+        a.bqkv = m->P(ab.qkv.b_off);
+        a.sqkv = m->P(ab.qkv.s_off);
+        a.q_slot = c.q_idx;
+        for (int d = 0; d < D; ++d) {
+            a.kv[d] = nullptr;
+            if (d == c.q_idx || !kvslot[d]) continue;
+            a.kv[d] = kvslot[d]; a.kv_bs[d] = HW * al.depth * 2 * C; a.kv_ld[d] = al.depth * 2 * C;
+            a.k_off[d] = i * 2 * C; a.v_off[d] = i * 2 * C + C;
+        }
+        a.kvpad = m->P(ab.kvpad_off);
+        a.biasT = m->P(ab.bias_off);
+        a.out = ws.ao;
+        a.out_bs = (long)ntile * 16 * C;
+        a.D = D; a.C = C; a.heads = c.num_heads; a.H = H; a.W = W; a.Hp = H + ph; a.Wp = W + pw;
+        a.pt = pt; a.pl = plft; a.nWw = (W + pw) / 7; a.dilated = dil ? 1 : 0; a.ntile = ntile;
+        { ProfScope ps(m, pname("wide_core", l), s); BDE_TRY(attn_tok16_launch(a, B, s)); }
+        float* dst = (last && out) ? out : (x == ws.xa ? ws.xb : ws.xa);     // out == nullptr: the caller only wants out_nchw
+        // x1 = shortcut + proj(attn)   (uncovered pixels of a dilated block: shortcut only; DTransformer.py:299, 79-82)
         BDE_TRY(run_tokgemm(m, "wide_proj", l, ab.projW, ab.proj, C, C, ws.ao, B, HW, nullptr, ws.x1, ACT_NONE, x, nullptr, nullptr,
-                            dil ? W : 0, pt, plft, 0, s));
+                            dil ? W : 0, pt, plft, s));
         // x2 = x1 + fc2(GELU(fc1(LN(x1))))  (+ merged[t] after the last block; DTransformer.py:279-283,304, V5.py:166)
         BDE_TRY(run_tokgemm(m, "wide_mlp_in", l, ab.fc1W, ab.fc1, 4 * C, C, ws.x1, B, HW, nullptr, ws.hid, ACT_GELU, nullptr, nullptr,
-                            nullptr, 0, 0, 0, 0, s));
-        }
+                            nullptr, 0, 0, 0, s));
         BDE_TRY(run_tokgemm(m, "wide_mlp_out", l, ab.fc2W, ab.fc2, C, 4 * C, ws.hid, B, HW, nullptr, dst, ACT_NONE, ws.x1,
-                            last ? addres : nullptr, last ? out_nchw : nullptr, 0, 0, 0, 0, s));
+                            last ? addres : nullptr, last ? out_nchw : nullptr, 0, 0, 0, s));
         x = dst;
     }
     return BDE_OK;
@@ -1140,8 +1092,8 @@ static int run_attention_level(bde_model* m, int l, int T, int B, int H, int W, 
     if (wide_ok(m, l)) {
         const int ntile = (int)cdivl(HW, 16);
         const long ffs = (long)B * ntile * 16 * C;           // FRAG16 frame stride
-        const long q0fs = (long)B * HW * 3 * C;
-        const bool twins = ws.mergedS[l] != nullptr && m->sb_terms == 2;
+        const bool twins = split_chain_ok(m, l);
+        BDE_REQUIRE(!twins || ws.mergedS[l], "wide split chain: the workspace has no SPL16 twins");
         const long sfs = ffs, stfs = (long)B * ntile * 16 * 2;    // SPL16 frame stride (floats of the image) / statistics stride
         {
             ProfScope ps(m, pname("to_frag", l), s);
@@ -1151,16 +1103,13 @@ static int run_attention_level(bde_model* m, int l, int T, int B, int H, int W, 
         }
         if (need_un)
             BDE_TRY(run_tokgemm(m, "wide_kv_all", l, al.kvallW, al.kvall, al.depth * 2 * C, C, ws.mergedT[l], T * B, HW, ws.kvun[l],
-                                nullptr, ACT_NONE, nullptr, nullptr, nullptr, 0, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
-        if (!m->wide_fuse_qkv)
-            BDE_TRY(run_tokgemm(m, "wide_qkv_all", l, al.blocks[0].qkvW, al.blocks[0].qkv, 3 * C, C, ws.mergedT[l], T * B, HW, ws.qkv0[l],
-                                nullptr, ACT_NONE, nullptr, nullptr, nullptr, 0, 0, 0, 0, s));
+                                nullptr, ACT_NONE, nullptr, nullptr, nullptr, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
         // one refined neighbour (one negative buffer offset): its K | V are computed by the attention core of the frame that reads
         // them (wide_core.h), from the neighbour's refined FRAG16 frame -- no K|V GEMM between two frames of the chain
         int nneg = 0, neg_slot = -1;
         for (int d = 0; d < D; ++d)
             if (d != c.q_idx && c.buffer_index[d] < 0) { ++nneg; neg_slot = d; }
-        const bool in_core = wide_core2_ok(m, l) && nneg == 1;
+        const bool in_core = twins && nneg == 1;
         for (int t = 0; t < T; ++t) {
             const float* kvslot[BDE_MAX_FRAMES];
             const float* prev_frag = nullptr;
@@ -1178,11 +1127,11 @@ static int run_attention_level(bde_model* m, int l, int T, int B, int H, int W, 
                 else kvslot[d] = ws.kvun[l] + (long)f * kvfs;
             }
             float* mtF = ws.mergedT[l] + (long)t * ffs;
-            BDE_TRY(run_attention_frame_wide(m, l, mtF, kvslot, mtF, mtF, ws.merged[l] + (long)t * fs, B, H, W, 0, al.depth,
-                                             ws.qkv0[l] + (long)t * q0fs, s, prev_frag, neg_slot, qt, qt, pt));
+            BDE_TRY(run_attention_frame_wide(m, l, mtF, kvslot, mtF, mtF, ws.merged[l] + (long)t * fs, B, H, W, 0, al.depth, s,
+                                             prev_frag, neg_slot, qt, qt, pt));
             if (need_ref && !in_core && t + 1 < T)
                 BDE_TRY(run_tokgemm(m, "wide_kv", l, al.kvallW, al.kvall, al.depth * 2 * C, C, mtF, B, HW, ws.kvref[l] + (long)t * kvfs,
-                                    nullptr, ACT_NONE, nullptr, nullptr, nullptr, 0, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
+                                    nullptr, ACT_NONE, nullptr, nullptr, nullptr, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
             if (on_frame) BDE_TRY(on_frame(m, t, ctx));
         }
         return BDE_OK;

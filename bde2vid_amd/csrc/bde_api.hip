@@ -34,7 +34,6 @@
 #include "wideblock.h"
 #include "wide_mlp.h"
 #include "wide_core.h"
-#include "attn_mfma.h"
 #include "conv_vec.h"
 #include "conv_sb.h"
 #include "voxel.h"
@@ -359,7 +358,6 @@ int bde_set_tuning(bde_model* m, const char* key, int64_t value) {
     }
     for (auto& w : m->wslots)
         if (w.graph_exec) { (void)hipGraphExecDestroy(w.graph_exec); w.graph_exec = nullptr; }
-    if (std::string(key) == "attn_mfma") { m->tune.attn_mfma = (int)value; return BDE_OK; }
     if (std::string(key) == "lstm_hc8") { m->lstm_hc8 = (int)value; return BDE_OK; }
     if (std::string(key) == "winblock") {
         if (m->winblock != (int)value)
@@ -368,24 +366,13 @@ int bde_set_tuning(bde_model* m, const char* key, int64_t value) {
         return BDE_OK;
     }
     if (std::string(key) == "winblock_sb") { m->winblock_sb = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide") {
-        if (m->wide != (int)value)
-            for (auto& w : m->wslots) w.release();
-        m->wide = (int)value;
+    if (std::string(key) == "wide_kv_sb" || std::string(key) == "wide_fuse_mlp") {    // one choice: split or fp32 chain (split_chain_ok)
+        int& v = std::string(key) == "wide_kv_sb" ? m->wide_kv_sb : m->wide_fuse_mlp;
+        if (v != (int)value)
+            for (auto& w : m->wslots) w.release();           // the SPL16 twins exist only for the split chain
+        v = (int)value;
         return BDE_OK;
     }
-    if (std::string(key) == "wide_fuse_qkv") { m->wide_fuse_qkv = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide_kv_sb") { m->wide_kv_sb = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide_fuse_mlp") { m->wide_fuse_mlp = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide_fuse_fc2") { m->wide_fuse_fc2 = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide_core2") {
-        if (m->wide_core2 != (int)value)
-            for (auto& w : m->wslots) w.release();           // the SPL16 twins exist only with it
-        m->wide_core2 = (int)value;
-        return BDE_OK;
-    }
-    if (std::string(key) == "wide_spl") { m->wide_spl = (int)value; return BDE_OK; }
-    if (std::string(key) == "wide_prefetch") { m->wide_prefetch = (int)value; return BDE_OK; }
     if (std::string(key) == "conv_sb") {
         if (m->conv_sb != (int)value)
             for (auto& w : m->wslots) w.release();           // which recurrent step runs (and its buffers) depends on it
@@ -452,7 +439,6 @@ int bde_get_info(const bde_model* m, const char* key, int64_t* value) {
     else if (k == "device") *value = m->device;
     else if (k == "winblock") *value = m->winblock;
     else if (k == "winblock_sb") *value = m->winblock_sb;
-    else if (k == "wide") *value = m->wide;
     else if (k == "conv_sb") *value = m->conv_sb;
     else if (k == "head3") *value = m->head3;
     else if (k == "lstm_sb") *value = m->lstm_sb_mode;
@@ -460,9 +446,11 @@ int bde_get_info(const bde_model* m, const char* key, int64_t* value) {
     else if (k == "lstm_fuse_x") *value = m->lstm_fuse_x;
     else if (k == "wide_kv_sb") *value = m->wide_kv_sb;
     else if (k == "wide_fuse_mlp") *value = m->wide_fuse_mlp;
-    else if (k == "wide_fuse_fc2") *value = m->wide_fuse_fc2;
-    else if (k == "wide_core2") *value = m->wide_core2;
-    else if (k == "wide_spl") *value = m->wide_spl;
+    else if (k == "wide_core2") {                                 // 1: a head_dim-16 level runs the split chain (wide_core_kernel)
+        int64_t v = 0;
+        for (int l = 0; l < m->L; ++l) v |= wide_ok(m, l) && split_chain_ok(m, l);
+        *value = v;
+    }
     else if (k == "sb_terms") *value = m->sb_terms;
     else if (k == "sb_auto") *value = m->sb_auto;
     else if (k == "sb_overflows") *value = m->sb_overflows;       // forwards settled so far whose two-term operands left fp16's range
@@ -827,7 +815,9 @@ int bde_op_dframe_attention(bde_model* m, int32_t level, const float* const* buf
         const long ffs = (long)B * cdivl(HW, 16) * 16 * C;
         int nneg = 0;
         for (int d = 0; d < D; ++d) nneg += d != c.q_idx && c.buffer_index[d] < 0;
-        const bool in_core = wide_core2_ok(m, level) && nneg == 1;
+        const bool split = split_chain_ok(m, level);
+        BDE_REQUIRE(!split || w.mergedS[level], "wide split chain: the workspace has no SPL16 twins");
+        const bool in_core = split && nneg == 1;
         const float* prev_frag = nullptr;
         int prev_slot = -1;
         WideTwin q_twin, p_twin;
@@ -835,9 +825,8 @@ int bde_op_dframe_attention(bde_model* m, int32_t level, const float* const* buf
             kvslot[d] = nullptr;
             if (bufs[d] == nullptr) continue;
             float* fr = w.mergedT[level] + (long)d * ffs;
-            const bool twins = w.mergedS[level] != nullptr && m->sb_terms == 2;
             WideTwin tw;
-            if (twins) {
+            if (split) {
                 tw = WideTwin{w.mergedS[level] + (long)d * ffs, w.mstats[level] + (long)d * B * cdivl(HW, 16) * 16 * 2};
                 BDE_TRY(nchw_to_frag_spl(bufs[d], fr, reinterpret_cast<unsigned short*>(tw.s), tw.st, B, C, (int)HW, m->ovf(), s));
             } else {
@@ -848,13 +837,13 @@ int bde_op_dframe_attention(bde_model* m, int32_t level, const float* const* buf
             if (in_core && c.buffer_index[d] < 0) { prev_frag = fr; prev_slot = d; p_twin = tw; continue; }
             float* dst = w.kvun[level] + (long)d * kvfs;
             BDE_TRY(run_tokgemm(m, "wide_kv", level, al.kvallW, al.kvall, al.depth * 2 * C, C, fr, B, HW, dst, nullptr, ACT_NONE, nullptr,
-                                nullptr, nullptr, 0, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
+                                nullptr, nullptr, 0, 0, 0, s, al.kvallH, al.kvallH_unscale));
             kvslot[d] = dst;
         }
         float* qf = w.mergedT[level] + (long)c.q_idx * ffs;
         // (the caller wants the result as NCHW only: the last block's SPL16 twin goes to a scratch pair)
-        return run_attention_frame_wide(m, level, qf, kvslot, nullptr, nullptr, out, B, H, W, first_block, nblocks, nullptr, s, prev_frag,
-                                        prev_slot, q_twin, q_twin.s ? WideTwin{w.xaS, w.stA} : WideTwin(), p_twin);
+        return run_attention_frame_wide(m, level, qf, kvslot, nullptr, nullptr, out, B, H, W, first_block, nblocks, s, prev_frag,
+                                        prev_slot, q_twin, split ? WideTwin{w.xaS, w.stA} : WideTwin(), p_twin);
     }
     for (int d = 0; d < D; ++d) {
         kvslot[d] = nullptr;

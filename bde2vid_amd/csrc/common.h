@@ -41,7 +41,6 @@ int fail(int code, const char* fmt, ...);
 // a thread-local pointer that every C-ABI entry point sets to ITS model for the duration of the call, so two models
 // (or two devices) in one process do not see each other's settings.
 struct Tuning {
-    int attn_mfma = 1;      // 0 = attn.h for every head_dim
     int conv_nt = 0;        // force 32-pixel tiles per wave (1 | 2), 0 = auto
     int conv_vec = 1;       // float4-staged convs
     int lstm_shape = 0;     // seg*100000 + rows*1000 + pxw, 0 = auto

@@ -1,12 +1,14 @@
-// Level-2 attention chain (head_dim 16, wideblock.h): the window half of a block -- q | k | v of the query frame's window tokens,
-// K | V of the REFINED neighbour frame's window tokens, softmax(q k^T + bias) v per (window, head) -- as one launch, second
-// generation of attn_tok16_kernel<true, true> (DTransformer.py:165-207; V5.py:154-169).
+// Level-2 attention chain (head_dim 16, wideblock.h): the window half of a block on the split chain -- q | k | v of the query
+// frame's window tokens, K | V of the REFINED neighbour frame's window tokens, softmax(q k^T + bias) v per (window, head) -- as one
+// launch (DTransformer.py:165-207; V5.py:154-169).  The fp32 chain's core is attn_tok16_kernel (wideblock.h).
 //
-// What changed, and why (attn_tok16_kernel measured 15.9 us per launch for ~1 us of matrix work):
+// Against a core that splits fp32 token fragments itself and streams its weights through registers (15.9 us per launch for ~1 us
+// of matrix work):
 //   * the head's q | k | v weight fragments (48 KB, two fp16 terms) come ONCE per workgroup, by LDS-DMA, all of them requested in
 //     the first instructions of the kernel together with every other operand (token fragments, bias tile, the other frames' K | V
 //     rows): one L2 round trip for everything instead of four register double-buffer rounds per wave, each wave re-fetching the
 //     same 48 KB;
+//   * the token operands arrive pre-split (SPL16, below): no split, running sums or zero masking in the GEMM loop;
 //   * the relative-position bias arrives as the score tiles' C operands (16-byte loads of a pre-packed table, as winblock.h)
 //     instead of 40 strided dword loads per lane;
 //   * K | V of the frame refined just before (buffer offset < 0, V5.py:166-169) are computed HERE from that frame's block output --
@@ -14,7 +16,7 @@
 //     tokens are one more token tile for fragments that are in LDS anyway -- which removes the K|V GEMM launch (26 us, 15 per
 //     forward) that sat between two frames of the sequential chain and its [T][HW][depth 2C] buffer.
 // Frames at offsets > 0 are still unrefined when they are needed: their K | V of all blocks come from one T-batched GEMM
-// (tokgemm_sb_kernel) as before.  Same arithmetic as attn_tok16_kernel<true, true>: two-term q|k|v GEMM, fp32 scores / softmax / p v.
+// (tokgemm_sb_rows_kernel).  Two-term q|k|v GEMM, fp32 scores / softmax / p v.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wideblock.h"
@@ -85,32 +87,24 @@ static int nchw_to_frag_spl(const float* in, float* frag, unsigned short* spl, f
 }
 
 struct WideCoreArgs {
-    const float* x;               // FRAG16 [B][ntile][C/16][256]: block input of the query frame
-    const float* xp;              // FRAG16: the refined neighbour frame (slot p_slot), nullptr = none handled here
-    long x_bs;
+    long x_bs;                    // batch stride of the FRAG16 output (elements)
     int q_slot, p_slot;           // buffer slots (key ranges slot * 49 ..) of the two
     const float* kv[ATT_MAXD];    // other slots: token-major rows holding K at +k_off[d], V at +v_off[d]; nullptr = zero frame
     long kv_bs[ATT_MAXD];
     int kv_ld[ATT_MAXD], k_off[ATT_MAXD], v_off[ATT_MAXD];
     const float* kvpad;           // [2C] K | V of a zero token
     const float* biasW;           // [heads][4 query tiles][10 key tiles][64 lanes][4]: score-tile C operands, keys slot-major, log2(e) folded
-    const unsigned short* wqkvS;  // q|k|v rows as two fp16 terms, k in FRAG16 group-pair order (TokGemmArgs::wS)
+    const unsigned short* wqkvS;  // q|k|v rows as two fp16 terms in natural k order (pack16_split)
     const float* wqkv_unscale;
     const float *bqkv, *sqkv;     // [3C] folded biases / row sums of the LayerNorm-folded weights
     float* out;                   // FRAG16 [B][ntile][C/16][256]: attention output
     int D, C, heads, H, W, Hp, Wp, pt, pl, nWw, dilated, ntile;
-    unsigned* ovf;                // range guard of the two-term format (split.h)
     unsigned long long* stamps;   // diagnostics only
-    // SPL = true: the two frames as SPL16 + statistics (above) instead of fp32 FRAG16; wqkvS then in natural k order
+    // the query frame and the refined neighbour frame (slot p_slot; xpS == nullptr: none handled here) as SPL16 + statistics (above)
     const unsigned short *xS, *xpS;
     const float *xSt, *xpSt;      // [B][ntile * 16][2]
     long spl_bs, st_bs;           // batch strides: 16-bit elements / floats
     const float* zeros;           // >= 16 bytes of zeros (operand of a padding token)
-    // L2 warm-up for the launch that follows on the chain (mlp_fused_kernel): its proj / fc1 weight fragments were last read one
-    // frame ago and have left the 4 MB L2s since.  Each workgroup touches its share of [pf_ptr, pf_ptr + pf_bytes) -- the workgroups of
-    // one XCD (every eighth in dispatch order) cover the whole range between them -- with loads nobody waits for.
-    const unsigned char* pf_ptr[2];
-    long pf_bytes[2];
 };
 #define WC_STAMP(i)                                                                                                  \
     do {                                                                                                             \
@@ -118,14 +112,11 @@ struct WideCoreArgs {
             a.stamps[(blockIdx.x * 4 + wave) * 8 + (i)] = __builtin_amdgcn_s_memtime();                               \
     } while (0)
 
-#ifndef WC_XCD_REMAP
-#define WC_XCD_REMAP 1
-#endif
 constexpr int WC_WL_BYTES = 3 * 8 * 2 * 1024;
 constexpr int WC_LDS_BYTES = WC_WL_BYTES + (2 * 10 * 16 * 16 + 2 * 48) * 4;      // 68.5 KB: two workgroups per CU
 
 // C = 256 (8 k-steps of 32), head_dim 16, D * 49 <= 160 keys.  grid (windows, heads, B), 256 threads = four query tiles.
-template <bool PREV, bool SPL>
+template <bool PREV>
 __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a) {
     constexpr int HD = 16, NT = 10, NKS = 8;
     extern __shared__ __align__(16) unsigned char wc_lds[];
@@ -144,11 +135,8 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
     {
         const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
         const unsigned lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        unsigned L = lin;
-        if (WC_XCD_REMAP) {
-            const unsigned xcd = lin & 7u, q = total >> 3, rem = total & 7u;
-            L = xcd * q + min(xcd, rem) + (lin >> 3);
-        }
+        const unsigned xcd = lin & 7u, q = total >> 3, rem = total & 7u;
+        const unsigned L = xcd * q + min(xcd, rem) + (lin >> 3);
         // (L < 2^20, divisors < 2^10: floor((L + 0.5) / d) through one v_rcp_f32 is exact -- an integer division by a run-time
         //  divisor is ~40 instructions, three of them at the head of every launch of the sequential chain)
         const unsigned q1 = (unsigned)(((float)L + 0.5f) * __builtin_amdgcn_rcpf((float)gx));
@@ -173,18 +161,11 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
     const int ngk = a.C >> 4;
 
     // ---- every operand of the launch is requested here ---------------------------------------------------------------------------
-    const long xo = ((long)(max(qpix, 0) >> 4) * ngk) * 64 + (max(qpix, 0) & 15) + 16 * g4;
-    const wf4* xw = reinterpret_cast<const wf4*>(a.x + b * a.x_bs) + xo;
-    // (fp32 token fragments: a rolling window of LA k-steps per token set is in flight -- all sixteen k-steps of both sets from
-    //  the start are 128 registers, which with two workgroups per CU is more than a wave has)
-    constexpr int LA = 4;
-    const wf4* xpw = (PREV && !SPL) ? reinterpret_cast<const wf4*>(a.xp + b * a.x_bs) + xo : xw;
-    wf4 xq[SPL ? 1 : 2 * NKS], xpv[(PREV && !SPL) ? 2 * NKS : 1];
     // SPL16 operands: the lane's 16 bytes of (k-step, term) of its token, 16 per token set, all requested here (a padding token
     // reads zeros: LayerNorm(0) = beta, i.e. the folded bias alone)
-    sb8 bqS[SPL ? NKS : 1][2], bpS[(SPL && PREV) ? NKS : 1][2];
+    sb8 bqS[NKS][2], bpS[PREV ? NKS : 1][2];
     float2 stq = {0.f, 1.f}, stp = {0.f, 1.f};
-    if constexpr (SPL) {
+    {
         const bool live = qpix >= 0;
         const long so = spl16_frag(max(qpix, 0) >> 4, NKS, 0, 0) + (max(qpix, 0) & 15) + 16 * g4;
         const int stride = live ? 64 : 0;
@@ -203,12 +184,6 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) bpS[ks][t] = sp[(ks * 2 + t) * stride];
             stp = *reinterpret_cast<const float2*>(live ? a.xpSt + b * a.st_bs + (long)qpix * 2 : reinterpret_cast<const float*>(a.zeros));
-        }
-    } else {
-#pragma unroll
-        for (int kg = 0; kg < 2 * LA; ++kg) {
-            xq[kg] = xw[kg * 64];
-            if constexpr (PREV) xpv[kg] = xpw[kg * 64];
         }
     }
     {
@@ -271,40 +246,9 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
     __syncthreads();
     const float us_qkv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, us_v)));
     WC_STAMP(1);
-    f32x4 pf_sink = {0.f, 0.f, 0.f, 0.f};     // destination of the warm-up loads: stays reserved until they have landed (end of the kernel)
-    if (a.pf_ptr[0] != nullptr && wave == 3) {
-        // (wave 3 holds one query of the window: the idlest of the four)
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned per_xcd = (gridDim.x * gridDim.y * gridDim.z + 7u) >> 3;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (a.pf_ptr[r] == nullptr) continue;
-            const long share = ((a.pf_bytes[r] / per_xcd) + 1023) & ~1023L;        // whole 1-KiB wave loads
-            const long beg = (long)(lin >> 3) * share;
-            for (long o = beg + lane * 16; o < min(beg + share, a.pf_bytes[r]); o += 1024)
-                asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pf_sink) : "v"(a.pf_ptr[r] + o) : "memory");
-        }
-    }
 
     // ---- q | k | v of this wave's token tile (query frame) and k | v of the same window tokens of the refined neighbour -------------
     f32x4 aq = {0.f, 0.f, 0.f, 0.f}, ak = aq, av = aq, akp = aq, avp = aq;
-    float s1 = 0.f, s2 = 0.f, p1 = 0.f, p2 = 0.f, gm = 0.f;
-    auto split_tile = [&](wf4 x0, wf4 x1, float& u1, float& u2, sb8 (&bfr)[2]) {
-        if (qpix < 0) x0 = x1 = wf4{0.f, 0.f, 0.f, 0.f};               // a zero token: LayerNorm(0) = beta, i.e. the folded bias alone
-        u1 += ((x0[0] + x0[1]) + (x0[2] + x0[3])) + ((x1[0] + x1[1]) + (x1[2] + x1[3]));
-        u2 += ((x0[0] * x0[0] + x0[1] * x0[1]) + (x0[2] * x0[2] + x0[3] * x0[3])) +
-              ((x1[0] * x1[0] + x1[1] * x1[1]) + (x1[2] * x1[2] + x1[3] * x1[3]));
-        unsigned t[4][2];
-        ws_split_pair_g<2>(x0[0], x0[1], t[0], gm);
-        ws_split_pair_g<2>(x0[2], x0[3], t[1], gm);
-        ws_split_pair_g<2>(x1[0], x1[1], t[2], gm);
-        ws_split_pair_g<2>(x1[2], x1[3], t[3], gm);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) bfr[q] = sb8{(int)t[0][q], (int)t[1][q], (int)t[2][q], (int)t[3][q]};
-        // (pins the running sums here: left free, the compiler sinks both chains of adds below the loop -- nothing needs them
-        //  earlier -- and keeps the eight fp32 values of every k-step alive for it: 64 registers per token set)
-        asm volatile("" : "+v"(u1), "+v"(u2), "+v"(gm));
-    };
     // The relative-position bias of this wave's score tiles (their C operands as 16-byte loads of the pre-packed table) is
     // requested half-way through the contraction: by then half of the token fragments' registers are free again, and the scores
     // are still a microsecond away.  Held from the start it costs 40 registers through the GEMM phase.
@@ -313,15 +257,6 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
         __builtin_amdgcn_sched_barrier(0);                             // (keeps the loads and LDS reads of later k-steps out of this one)
-        if constexpr (!SPL) {
-            if (ks + LA < NKS) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    xq[2 * (ks + LA) + h] = xw[(2 * (ks + LA) + h) * 64];
-                    if constexpr (PREV) xpv[2 * (ks + LA) + h] = xpw[(2 * (ks + LA) + h) * 64];
-                }
-            }
-        }
         if (ks == NKS / 2) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) sc[j] = biasp[j * 64];
@@ -333,43 +268,20 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
             fk[t] = *reinterpret_cast<const sb8*>(WL + ((1 * NKS + ks) * 2 + t) * 1024 + lane * 16);
             fv[t] = *reinterpret_cast<const sb8*>(WL + ((2 * NKS + ks) * 2 + t) * 1024 + lane * 16);
         }
-        if constexpr (SPL) {
-            aq = sb_mma16<2>(fq, bqS[ks], aq);
-            ak = sb_mma16<2>(fk, bqS[ks], ak);
-            av = sb_mma16<2>(fv, bqS[ks], av);
-            if constexpr (PREV) {
-                akp = sb_mma16<2>(fk, bpS[ks], akp);
-                avp = sb_mma16<2>(fv, bpS[ks], avp);
-            }
-        } else {
-            sb8 bq[2];
-            split_tile(xq[2 * ks], xq[2 * ks + 1], s1, s2, bq);
-            aq = sb_mma16<2>(fq, bq, aq);
-            ak = sb_mma16<2>(fk, bq, ak);
-            av = sb_mma16<2>(fv, bq, av);
-            if constexpr (PREV) {
-                sb8 bp[2];
-                split_tile(xpv[2 * ks], xpv[2 * ks + 1], p1, p2, bp);
-                akp = sb_mma16<2>(fk, bp, akp);
-                avp = sb_mma16<2>(fv, bp, avp);
-            }
+        aq = sb_mma16<2>(fq, bqS[ks], aq);
+        ak = sb_mma16<2>(fk, bqS[ks], ak);
+        av = sb_mma16<2>(fv, bqS[ks], av);
+        if constexpr (PREV) {
+            akp = sb_mma16<2>(fk, bpS[ks], akp);
+            avp = sb_mma16<2>(fv, bpS[ks], avp);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!SPL) sb_guard_flush(gm, a.ovf);       // (SPL16 frames were checked when they were written)
     WC_STAMP(2);
     wf4 qv;
     {
         const float us = us_qkv;
-        auto stats = [&](float u1, float u2, float& mean, float& rstd) {
-            u1 += __shfl_xor(u1, 16); u2 += __shfl_xor(u2, 16);
-            u1 += __shfl_xor(u1, 32); u2 += __shfl_xor(u2, 32);
-            mean = u1 / (float)a.C;
-            rstd = __builtin_amdgcn_rsqf(fmaxf(u2 / (float)a.C - mean * mean, 0.f) + 1e-5f);
-        };
-        float mean, rstd;
-        if constexpr (SPL) { mean = stq.x; rstd = qpix >= 0 ? stq.y : 1.f; }
-        else stats(s1, s2, mean, rstd);
+        const float mean = stq.x, rstd = qpix >= 0 ? stq.y : 1.f;
         float kq[4], vq[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -386,9 +298,7 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
             *reinterpret_cast<wf4*>(VL + u * HD + g4 * 4) = wf4{vq[0], vq[1], vq[2], vq[3]};
         }
         if constexpr (PREV) {
-            float meanp, rstdp;
-            if constexpr (SPL) { meanp = stp.x; rstdp = qpix >= 0 ? stp.y : 1.f; }
-            else stats(p1, p2, meanp, rstdp);
+            const float meanp = stp.x, rstdp = qpix >= 0 ? stp.y : 1.f;
             if (qi < ATT_TOK) {
                 const int u = a.p_slot * ATT_TOK + qi;
                 float vp[4];
@@ -415,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
     }
     __syncthreads();
     WC_STAMP(3);
-    // ---- scores^T = k q^T + bias, softmax over the keys, out^T = v^T p^T (attn_mfma.h) ---------------------------------------------
+    // ---- scores^T = k q^T + bias, softmax over the keys, out^T = v^T p^T (as attn_tok16_kernel) --------------------------------
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -455,26 +365,21 @@ __global__ __launch_bounds__(256, 2) void wide_core_kernel(const WideCoreArgs a)
         for (int r = 0; r < 4; ++r) op[r * 64] = acc[r] * inv;
     }
     WC_STAMP(6);
-    // (an asynchronous load may not outlive the reservation of its destination register)
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf_sink)::"memory");
 }
 
 static int wide_core_launch(const WideCoreArgs& a, int B, hipStream_t s) {
     if (a.C != 256 || a.heads * 16 != a.C || a.D * ATT_TOK > 160)
         return fail(BDE_ERR_UNSUPPORTED, "wide attention core: C = %d, %d heads, D = %d", a.C, a.heads, a.D);
     const int nW = (a.Hp / ATT_WS) * (a.Wp / ATT_WS);
-    static unsigned char raised[4][BDE_MAX_DEVICES];
-    const bool spl = a.xS != nullptr;
+    static unsigned char raised[2][BDE_MAX_DEVICES];
     const dim3 grid(nW, a.heads, B);
-#define WC_LAUNCH(P, S, i)                                                                                          \
+#define WC_LAUNCH(P, i)                                                                                             \
     do {                                                                                                            \
-        BDE_HIP(raise_dynamic_lds(raised[i], (const void*)wide_core_kernel<P, S>, WC_LDS_BYTES));                    \
-        hipLaunchKernelGGL((wide_core_kernel<P, S>), grid, dim3(256), WC_LDS_BYTES, s, a);                          \
+        BDE_HIP(raise_dynamic_lds(raised[i], (const void*)wide_core_kernel<P>, WC_LDS_BYTES));                       \
+        hipLaunchKernelGGL((wide_core_kernel<P>), grid, dim3(256), WC_LDS_BYTES, s, a);                             \
     } while (0)
-    if (a.xp && spl) WC_LAUNCH(true, true, 0);
-    else if (a.xp) WC_LAUNCH(true, false, 1);
-    else if (spl) WC_LAUNCH(false, true, 2);
-    else WC_LAUNCH(false, false, 3);
+    if (a.xpS) WC_LAUNCH(true, 0);
+    else WC_LAUNCH(false, 1);
 #undef WC_LAUNCH
     BDE_HIP(hipGetLastError());
     return BDE_OK;

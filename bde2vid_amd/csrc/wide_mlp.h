@@ -1,10 +1,10 @@
 // Level-2 attention chain (head_dim 16, 256 channels, wideblock.h): the token half of a block -- x1 = x + proj(attention output),
 // hidden = GELU(fc1(LayerNorm2(x1))), x2 = x1 + fc2(hidden) (+ merged[t]) (DTransformer.py:299, 279-283, 304; V5.py:166) -- as ONE
-// launch on the sequential chain of V5.py:154-169 instead of two (projfc1_sb_kernel + the fc2 GEMM).
+// launch on the sequential chain of V5.py:154-169 (the split chain; the fp32 chain runs three tokgemm_kernel launches).
 //
 // What bounds these launches is not arithmetic (0.8 GFLOP) but how many weight bytes a CU can have in flight: a workgroup of four
 // waves that owns 16 tokens streams 0.75 MB of two-term weight fragments (proj 256 KB, a quarter of fc1 and of fc2 256 KB each)
-// from L2, and with 8 fragments (8 KB) per wave in flight a CU pulls ~35 GB/s (512 KB in 13 us: what projfc1_sb_kernel measured).
+// from L2, and with 8 fragments (8 KB) per wave in flight a CU pulls ~35 GB/s (512 KB in 13 us: what a fused proj + fc1 launch measured).
 //   * Every wave runs its three GEMM phases as ONE stream of 24 k-step groups (8 per phase; a group = the wave's four 16-row
 //     tiles x two terms = 8 fragments of 1 KB) with the fragments of PD groups ahead in registers: 24-32 KB per wave, ~100 KB per
 //     CU in flight, across the phase boundaries (the barriers between phases wait for LDS only, never for the stream).
@@ -16,7 +16,6 @@
 //     the result does not depend on which workgroup that is), adds merged[t] and stores x2.  Hand-off as MI355X_MICROARCH.md
 //     prescribes for a last-arriver: 16-byte sc1 stores, every storing wave's vmcnt(0), workgroup barrier, ONE agent-scope atomic
 //     add per workgroup on one counter per token tile, sc1 loads by the workgroup whose add returned 3.  Nobody waits for anybody.
-// Results are those of the two launches it replaces up to fp32 summation order (fc2's K is summed per quarter).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -71,17 +70,11 @@ __device__ __forceinline__ f32x4 ld_sc1_f4(const float* p) {
     return v;
 }
 
-#ifndef WM_PD
-#define WM_PD 3
-#endif
-#ifndef WM_XCD_REMAP
-#define WM_XCD_REMAP 1
-#endif
 // C = 256 channels, hidden = 1024.  grid (token tiles, 4 quarters of the hidden rows, B), 256 threads.
 __global__ __launch_bounds__(256) void mlp_fused_kernel(const MlpFusedArgs a) {
     constexpr int NKS = 8;                 // k-steps of 32 per phase (K = 256 per workgroup in all three GEMMs)
     constexpr int NG = 3 * NKS;            // k-step groups of the wave's fragment stream
-    constexpr int PD = WM_PD;              // groups in flight ahead of the one being contracted
+    constexpr int PD = 3;                  // groups in flight ahead of the one being contracted
     constexpr int RING = PD + 1;
     __shared__ __align__(16) unsigned char X1S[NKS * 2 * 1024];   // x1 as split B fragments [k-step][term][64 lanes][16 B]
     __shared__ __align__(16) unsigned char HS[NKS * 2 * 1024];    // this quarter's hidden activations likewise
@@ -97,11 +90,8 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(const MlpFusedArgs a) {
     {
         const unsigned gx = gridDim.x, total = gx * 4u * gridDim.z;
         const unsigned lin = blockIdx.x + gx * (blockIdx.y + 4u * blockIdx.z);
-        unsigned L = lin;
-        if (WM_XCD_REMAP) {
-            const unsigned xcd = lin & 7u, q = total >> 3, rem = total & 7u;
-            L = xcd * q + min(xcd, rem) + (lin >> 3);
-        }
+        const unsigned xcd = lin & 7u, q = total >> 3, rem = total & 7u;
+        const unsigned L = xcd * q + min(xcd, rem) + (lin >> 3);
         const unsigned q1 = (unsigned)(((float)L + 0.5f) * __builtin_amdgcn_rcpf((float)gx));   // (exact: wide_core.h)
         tile = (int)(L - q1 * gx);
         quarter = (int)(q1 & 3u);

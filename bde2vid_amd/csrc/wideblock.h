@@ -1,6 +1,6 @@
 // Temporal window attention for WIDE levels (head_dim 16: 256 channels / 16 heads at level 2 of the canonical config),
 // where a frame is only a few hundred tokens (23 x 30 at 184 x 240) and the five launches of a block sit on the sequential
-// chain of V5.py:154-169.  The split path (pw_gemm.h + attn_mfma.h) ran each of them in 10-13.5 us for < 1 us of matrix
+// chain of V5.py:154-169.  The generic path (pw_gemm.h + attn.h) ran each of them in 10-13.5 us for < 1 us of matrix
 // work: NCHW planes make every operand fetch a gather of 28-byte runs, and every wave fetched its operands with dword
 // loads.  Here the chain keeps its activations in the layout the matrix cores consume:
 //
@@ -8,18 +8,20 @@
 //            [channel 16*group + 4*j + g4] -- i.e. the tensor IS the sequence of B fragments of v_mfma_f32_16x16x4_f32,
 //            four k-steps per 16-byte load, 1 KiB per wave instruction, no LDS staging and no transposition anywhere.
 //            The D fragments of the producing GEMM land in it with four 256-byte stores per 16 x 16 tile.
-//   token-major [token][channels] for q|k|v, which the attention core gathers per window token (64 contiguous bytes per
+//   token-major [token][channels] for the K|V stacks, which the attention cores gather per window token (64 contiguous bytes per
 //            head instead of 16 scattered dwords).
 //
 //   tokgemm_kernel<MT, NT, KSPLIT>   out = epilogue(W x): weights pre-packed in the same four-k-steps-per-load order;
 //            LayerNorm folded as in pw_gemm.h (Linear(LN(x)) = rstd (W'x - mu s) + b', statistics from the streamed B
 //            fragments); epilogues: token-major store (q|k|v, K|V stacks) or FRAG16 store with GELU / residual /
 //            dilated-coverage mask / merged[t] / a second NCHW copy for the decoder.
-//   attn_tok16_kernel   softmax(q k^T + bias) v per (window, head) on the matrix cores as attn_mfma.h, reading token-major
-//            q|k|v with 16-byte loads and writing its output straight into FRAG16.
+//   tokgemm_sb_rows_kernel / tokgemm_sb_kernel   the K|V GEMMs of the split chain on two-term fp16 operands (split.h).
+//   attn_tok16_kernel   the fp32 chain's attention core: q|k|v of the query frame, then softmax(q k^T + bias) v per (window,
+//            head) on the matrix cores, reading the other frames' K|V token-major with 16-byte loads and writing its output
+//            straight into FRAG16.  The split chain's core and MLP are wide_core.h and wide_mlp.h.
 //
 // Restates DTransformer.py:165-207 (WindowAttention3D), :254-306 (SwinTransformerBlock3D) and :19-37 (Mlp) exactly as the
-// split path does (same folded weights, same bias tables, same padding / dilation rules).
+// generic path does (same folded weights, same bias tables, same padding / dilation rules).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "attn.h"
@@ -445,23 +447,9 @@ __global__ __launch_bounds__(256) void tokgemm_sb_kernel(const TokGemmArgs a) {
 // (sixteen B fragments, 64 registers), computes its LayerNorm statistics once and then walks RGN groups of four row tiles: one stream of
 // weight fragments (the four waves of a workgroup ask for the same ones: L1), MFMAs and 16-byte stores.  The sum over k runs in the
 // same order as in tokgemm_sb_kernel: identical results.  K = 256.
-#ifndef TOKGEMM_SB_RGN
-#define TOKGEMM_SB_RGN 6
-#endif
-#ifndef TOKGEMM_SB_PD
-#define TOKGEMM_SB_PD 3
-#endif
-#ifndef TOKGEMM_SB_MT
-#define TOKGEMM_SB_MT 4
-#endif
-#ifndef TOKGEMM_SB_NTT
-#define TOKGEMM_SB_NTT 2
-#endif
-#ifndef TOKGEMM_SB_OCC
-#define TOKGEMM_SB_OCC 1
-#endif
+constexpr int TOKGEMM_SB_RGN = 6, TOKGEMM_SB_MT = 4, TOKGEMM_SB_NTT = 2;
 template <int RGN, int MT, int NTT>
-__global__ __launch_bounds__(256, TOKGEMM_SB_OCC) void tokgemm_sb_rows_kernel(const TokGemmArgs a) {
+__global__ __launch_bounds__(256, 1) void tokgemm_sb_rows_kernel(const TokGemmArgs a) {
     // NTT token tiles per wave: every weight fragment feeds NTT MFMAs -- the four waves of a workgroup walk the same rows, and each pulls
     // its own copy of the fragments through the CU's vector-memory return path (64 B/clk): that path, not the matrix pipe, is what one
     // token tile per wave was bound by (128 us at any occupancy, prefetch depth or store pattern).
@@ -478,7 +466,7 @@ __global__ __launch_bounds__(256, TOKGEMM_SB_OCC) void tokgemm_sb_rows_kernel(co
     const float* lsum = a.lnsum ? a.lnsum : a.bias;        // (pointer select: no load under a branch)
     // weight fragments run PD k-steps ahead of the MFMAs in a ring of PD + 1 register sets (8 steps per group: a step's ring position is
     // a compile-time constant); one wave per SIMD at this register count, so the distance has to cover an L2 round trip by itself
-    constexpr int PD = TOKGEMM_SB_PD, RING = PD + 1;
+    constexpr int PD = 3, RING = PD + 1;
     static_assert(KS % RING == 0, "ring position of a k-step must not depend on the group");
     sb8 av[RING][MT][2];
 #pragma unroll
@@ -603,11 +591,9 @@ static bool tokgemm_sb_fits(const TokGemmArgs& a) {
 }
 static int tokgemm_sb_launch(const TokGemmArgs& a, int B, hipStream_t s) {
     const int ngm = a.M / 16;
-    const long tiles = (long)a.ntile * ngm * B;
     // (eight row tiles per wave would halve the split work per MFMA on the T-batched launch, but need 239 + 32 registers: one wave
     //  per SIMD; four row tiles: 212, two waves)
-    (void)tiles;
-    if (TOKGEMM_SB_RGN > 0 && a.K == 256 && (long)a.ntile * B >= 256 && ngm >= TOKGEMM_SB_MT * TOKGEMM_SB_RGN) {
+    if (a.K == 256 && (long)a.ntile * B >= 256 && ngm >= TOKGEMM_SB_MT * TOKGEMM_SB_RGN) {
         // the T-batched launch: a wave keeps its split token tiles and walks TOKGEMM_SB_RGN groups of TOKGEMM_SB_MT row tiles
         hipLaunchKernelGGL((tokgemm_sb_rows_kernel<TOKGEMM_SB_RGN, TOKGEMM_SB_MT, TOKGEMM_SB_NTT>),
                            dim3(cdiv(a.ntile, 4 * TOKGEMM_SB_NTT), cdiv(ngm, TOKGEMM_SB_MT * TOKGEMM_SB_RGN), B), dim3(256), 0, s, a);
@@ -615,165 +601,6 @@ static int tokgemm_sb_launch(const TokGemmArgs& a, int B, hipStream_t s) {
         return BDE_OK;
     }
     hipLaunchKernelGGL(tokgemm_sb_kernel<4>, dim3(cdiv(a.ntile, 4), cdiv(ngm, 4), B), dim3(256), 0, s, a);
-    BDE_HIP(hipGetLastError());
-    return BDE_OK;
-}
-
-// x1 = x + proj(attention output) AND hidden = GELU(fc1(LayerNorm2(x1))) in ONE launch of the sequential chain
-// (DTransformer.py:299, 279-283): fc1 needs every channel of a token's x1, so the two GEMMs used to be two launches of 8-9 us for
-// 0.09 + 0.36 GFLOP.  With two-term operands (split.h) the proj of a 16-token tile is 384 MFMAs of 16 cycles: cheap enough to
-// REPEAT in each of the four workgroups that share a token tile's fc1 rows (grid = token tiles x 4 quarters of the hidden rows).
-// A workgroup: proj of its token tile (16 row tiles over four waves) -> x1 into LDS in FRAG16 order (quarter 0 also stores it: the
-// residual of fc2) + LayerNorm sums -> barrier -> its 16 fc1 row tiles with x1 as the token operand, GELU, FRAG16 store.
-// Token operands are split in registers as in tokgemm_sb_kernel; weights in the k order of FRAG16 group pairs (TokGemmArgs::wS).
-// C = 256, hidden = 1024 (level 2 of config A).
-struct ProjFc1Args {
-    const float* ao;              // FRAG16 [B][ntile][C/16][256]: attention output
-    const float* x;               // FRAG16, same shape: the block input (shortcut)
-    const unsigned short *wprojS, *wfc1S;
-    const float *proj_unscale, *fc1_unscale;
-    const float* bproj;           // [C]
-    const float *bfc1, *sfc1;     // [hidden] folded bias, row sums of the LayerNorm-folded weights
-    float* x1;                    // FRAG16 [B][ntile][C/16][256]
-    float* hid;                   // FRAG16 [B][ntile][hidden/16][256]
-    long x_bs, hid_bs;
-    int C, hidden, HW, ntile;
-    int mask_w, mask_pt, mask_pl; // dilated-window coverage mask on the proj output (uncovered pixels: shortcut only)
-    unsigned* ovf;                // range guard of the two-term format (split.h)
-};
-// acc[m] += W[row tiles rt0 .. rt0 + 3] x over K = 32 nks; xp = the lane's wf4 of channel group 0 (consecutive groups 64 wf4 apart)
-template <typename XP>
-__device__ __forceinline__ void frag_gemm4(XP xp, const sb8* wbase, int rt0, int nks, f32x4 (&acc)[4], float& gm) {
-    constexpr int KS = 8;
-    const sb8* wp[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) wp[m] = wbase + ((long)(rt0 + m) * nks * 2) * 64;
-    for (int k0 = 0; k0 < nks; k0 += KS) {
-        wf4 xv[KS][2];
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-            const int ks = min(k0 + k, nks - 1);
-            xv[k][0] = xp[(2 * ks) * 64];
-            xv[k][1] = xp[(2 * ks + 1) * 64];
-        }
-        sb8 av[2][4][2];
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) av[0][m][t] = wp[m][((long)k0 * 2 + t) * 64];
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-            if (k + 1 < KS) {
-                const int ks = min(k0 + k + 1, nks - 1);
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) av[(k + 1) & 1][m][t] = wp[m][((long)ks * 2 + t) * 64];
-            }
-            if (k0 + k < nks) {
-                const wf4 x0 = xv[k][0], x1 = xv[k][1];
-                unsigned t[4][2];
-                ws_split_pair_g<2>(x0[0], x0[1], t[0], gm);
-                ws_split_pair_g<2>(x0[2], x0[3], t[1], gm);
-                ws_split_pair_g<2>(x1[0], x1[1], t[2], gm);
-                ws_split_pair_g<2>(x1[2], x1[3], t[3], gm);
-                sb8 bfr[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) bfr[q] = sb8{(int)t[0][q], (int)t[1][q], (int)t[2][q], (int)t[3][q]};
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = sb_mma16<2>(av[k & 1][m], bfr, acc[m]);
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void projfc1_sb_kernel(const ProjFc1Args a) {
-    __shared__ __align__(16) float X1[16 * 256];           // x1 of the token tile, FRAG16 order [C/16][64 lanes][4]
-    __shared__ float ST[4][16][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g4 = lane >> 4, col = lane & 15;
-    const int tile = blockIdx.x, quarter = blockIdx.y, b = blockIdx.z;
-    const int ngc = a.C >> 4, ngh = a.hidden >> 4, nks = a.C >> 5;
-    const int tok = tile * 16 + col;
-    // ---- x1 = x + proj(ao): row tiles 4 wave .. 4 wave + 3 -------------------------------------------------------------------
-    {
-        const wf4* ap = reinterpret_cast<const wf4*>(a.ao + b * a.x_bs) + ((long)tile * ngc) * 64 + lane;
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float xr[4][4], bp[4][4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int rt = 4 * wave + m;
-            const long fo = ((long)tile * ngc + rt) * 256 + col * 4 + g4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xr[m][r] = a.x[b * a.x_bs + fo + r * 64];
-                bp[m][r] = a.bproj[rt * 16 + g4 * 4 + r];
-            }
-        }
-        float gm = 0.f;
-        frag_gemm4(ap, reinterpret_cast<const sb8*>(a.wprojS) + lane, 4 * wave, nks, acc, gm);
-        sb_guard_flush(gm, a.ovf);
-        bool covered = true;
-        if (a.mask_w > 0 && tok < a.HW) {
-            const int y = tok / a.mask_w, x = tok - y * a.mask_w;
-            const int rr = y + a.mask_pt, cc = x + a.mask_pl;
-            covered = !((rr < 7 && (rr & 1)) || (cc < 7 && (cc & 1)));
-        }
-        const float us = a.proj_unscale[0];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int rt = 4 * wave + m;
-            const long fo = ((long)tile * ngc + rt) * 256 + col * 4 + g4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float v = (covered ? acc[m][r] * us + bp[m][r] : 0.f) + xr[m][r];
-                X1[(rt * 64 + col + 16 * r) * 4 + g4] = v;
-                if (quarter == 0) a.x1[b * a.x_bs + fo + r * 64] = v;
-                s1 += v;
-                s2 += v * v;
-            }
-        }
-        s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-        s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-        if (lane < 16) { ST[wave][lane][0] = s1; ST[wave][lane][1] = s2; }
-    }
-    __syncthreads();
-    // ---- hidden = GELU(fc1(LayerNorm2(x1))): row tiles 16 quarter + 4 wave .. + 3 ---------------------------------------------
-    {
-        const float u = (ST[0][col][0] + ST[1][col][0]) + (ST[2][col][0] + ST[3][col][0]);       // (fixed order: every workgroup
-        const float v = (ST[0][col][1] + ST[1][col][1]) + (ST[2][col][1] + ST[3][col][1]);       //  of a tile gets the same sums)
-        const float mean = u / (float)a.C;
-        const float rstd = __builtin_amdgcn_rsqf(fmaxf(v / (float)a.C - mean * mean, 0.f) + 1e-5f);
-        const int rt0 = 16 * quarter + 4 * wave;
-        float bb[4][4], ss[4][4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bb[m][r] = a.bfc1[(rt0 + m) * 16 + g4 * 4 + r];
-                ss[m][r] = a.sfc1[(rt0 + m) * 16 + g4 * 4 + r];
-            }
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float gm = 0.f;
-        frag_gemm4(reinterpret_cast<const wf4*>(X1) + lane, reinterpret_cast<const sb8*>(a.wfc1S) + lane, rt0, nks, acc, gm);
-        sb_guard_flush(gm, a.ovf);
-        const float us = a.fc1_unscale[0];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const long fo = ((long)tile * ngh + rt0 + m) * 256 + col * 4 + g4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                a.hid[b * a.hid_bs + fo + r * 64] = gelu_f(rstd * (acc[m][r] * us - mean * ss[m][r]) + bb[m][r]);
-        }
-    }
-}
-static int projfc1_sb_launch(const ProjFc1Args& a, int B, hipStream_t s) {
-    if (a.C != 256 || a.hidden != 1024) return fail(BDE_ERR_UNSUPPORTED, "fused proj + fc1: C = %d, hidden = %d", a.C, a.hidden);
-    hipLaunchKernelGGL(projfc1_sb_kernel, dim3(a.ntile, 4, B), dim3(256), 0, s, a);
     BDE_HIP(hipGetLastError());
     return BDE_OK;
 }
@@ -797,39 +624,31 @@ static int tokgemm_launch(const TokGemmArgs& a, int B, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 struct AttnTokArgs {
-    const float* q;               // token-major [B][HW][q_ld]: the query frame's q | k | v rows
     const float* kv[ATT_MAXD];    // per slot: token-major rows holding K at +k_off[d], V at +v_off[d]; nullptr = zero frame
-    long q_bs, kv_bs[ATT_MAXD];
-    int q_ld, kv_ld[ATT_MAXD], k_off[ATT_MAXD], v_off[ATT_MAXD];
+    long kv_bs[ATT_MAXD];         // (the query frame's slot is ignored: its rows are computed here)
+    int kv_ld[ATT_MAXD], k_off[ATT_MAXD], v_off[ATT_MAXD];
     const float* kvpad;           // [2C] K | V of a zero token
     const float* biasT;           // [heads][D*49][49], query index fastest, log2(e) folded
     float* out;                   // FRAG16 [B][ntile][C/16][256]
     long out_bs;
     int D, C, heads, H, W, Hp, Wp, pt, pl, nWw, dilated, ntile;
-    // FUSE: q | k | v of the query frame are computed here from the block input instead of read from `q` / kv[q_slot]
+    // q | k | v of the query frame are computed here from the block input
     const float* x;               // FRAG16 [B][ntile][C/16][256]: the block input (current x of the query frame)
     long x_bs;
     const float* wqkv;            // packed as for tokgemm_kernel: [3C/16][C/16][256]; rows q | k | v, LayerNorms folded
     const float* bqkv;            // [3C] folded biases
     const float* sqkv;            // [3C] row sums of the folded weights
     int q_slot;                   // buffer slot of the query frame
-    // SPLIT: the same rows as two fp16 terms in the k order of FRAG16 group pairs (TokGemmArgs::wS), *wqkv_unscale their inverse scale
-    const unsigned short* wqkvS;
-    const float* wqkv_unscale;
-    unsigned* ovf;                // range guard of the two-term format (split.h)
 };
 
-// softmax(q k^T + bias) v for one (window, head), head_dim 16; four waves = four tiles of 16 queries (attn_mfma.h).
+// softmax(q k^T + bias) v for one (window, head), head_dim 16, on the fp32 chain; four waves = four tiles of 16 queries.
 // The 16 channels of the head are contracted in the order (4 g4 + ks): a lane's 16-byte load of q is then its four
 // B-operand values as they stand, and K is staged into LDS rows in the same order.
-// FUSE: the workgroup first computes q | k | v of its head for the window's 49 tokens of the query frame -- three row tiles of the
+// The workgroup first computes q | k | v of its head for the window's 49 tokens of the query frame -- three row tiles of the
 // q|k|v GEMM, K = C, wave = token tile, operand fragments gathered straight from the FRAG16 block input (a window token's
 // fragment is one 16-byte load per lane and channel group) -- instead of a GEMM launch of its own in front of this one
 // (8.9 us on the sequential chain for 0.36 GFLOP).  The D fragments ARE what the attention wants: q as the score MFMA's B
 // operand, K and V as the LDS rows below; the per-(window, head) split repeats no work.
-// SPLIT (with FUSE): that GEMM on the fp16 matrix cores with two-term operands (split.h), the window tokens split in registers as in
-// tokgemm_sb_kernel: 72 MFMAs of 16 cycles per wave instead of 192 of 32.
-template <bool FUSE, bool SPLIT>
 __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
     constexpr int HD = 16, NT = 10;
     __shared__ __align__(16) float KL[NT * HD * 16];
@@ -850,7 +669,7 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
     const int qi = wave * 16 + col;
     const int qpix = qi < ATT_TOK ? token_pixel(qi) : -1;
     wf4 qv;
-    if constexpr (FUSE) {
+    {
         // rows head (q), C/16 + head (k), 2C/16 + head (v) of the packed q|k|v weights; this wave's token tile = queries 16 wave ..
         const int ngk = a.C >> 4;
         const wf4* xw = reinterpret_cast<const wf4*>(a.x + b * a.x_bs) + ((long)(max(qpix, 0) >> 4) * ngk) * 64 + (max(qpix, 0) & 15) + 16 * g4;
@@ -860,64 +679,7 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
         f32x4 aq = {0.f, 0.f, 0.f, 0.f}, ak = aq, av = aq;
         float s1 = 0.f, s2 = 0.f;
         const bool any = wave * 16 < ATT_TOK;                      // (tile 3 holds token 48 only; a tile past the window is skipped)
-        if (SPLIT && any) {
-            const int nks = a.C >> 5;
-            const sb8* wqS = reinterpret_cast<const sb8*>(a.wqkvS) + ((long)head * nks * 2) * 64 + lane;
-            const sb8* wkS = reinterpret_cast<const sb8*>(a.wqkvS) + ((long)(ngk + head) * nks * 2) * 64 + lane;
-            const sb8* wvS = reinterpret_cast<const sb8*>(a.wqkvS) + ((long)(2 * ngk + head) * nks * 2) * 64 + lane;
-            constexpr int U = 2;                                   // k-steps of 32 (two channel groups each) per register buffer
-            float gm = 0.f;
-            wf4 xb[2][2 * U];
-            sb8 fq[2][U][2], fk[2][U][2], fv[2][U][2];
-            auto fetch = [&](int buf, int ks0) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const long ks = min(ks0 + u, nks - 1);
-                    xb[buf][2 * u] = xw[(2 * ks) * 64];
-                    xb[buf][2 * u + 1] = xw[(2 * ks + 1) * 64];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        fq[buf][u][t] = wqS[(ks * 2 + t) * 64];
-                        fk[buf][u][t] = wkS[(ks * 2 + t) * 64];
-                        fv[buf][u][t] = wvS[(ks * 2 + t) * 64];
-                    }
-                }
-            };
-            auto compute = [&](int buf, int ks0) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (ks0 + u >= nks) continue;
-                    wf4 x0 = xb[buf][2 * u], x1 = xb[buf][2 * u + 1];
-                    if (qpix < 0) x0 = x1 = wf4{0.f, 0.f, 0.f, 0.f};
-                    s1 += ((x0[0] + x0[1]) + (x0[2] + x0[3])) + ((x1[0] + x1[1]) + (x1[2] + x1[3]));
-                    s2 += ((x0[0] * x0[0] + x0[1] * x0[1]) + (x0[2] * x0[2] + x0[3] * x0[3])) +
-                          ((x1[0] * x1[0] + x1[1] * x1[1]) + (x1[2] * x1[2] + x1[3] * x1[3]));
-                    unsigned t[4][2];
-                    ws_split_pair_g<2>(x0[0], x0[1], t[0], gm);
-                    ws_split_pair_g<2>(x0[2], x0[3], t[1], gm);
-                    ws_split_pair_g<2>(x1[0], x1[1], t[2], gm);
-                    ws_split_pair_g<2>(x1[2], x1[3], t[3], gm);
-                    sb8 bfr[2];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) bfr[q] = sb8{(int)t[0][q], (int)t[1][q], (int)t[2][q], (int)t[3][q]};
-                    aq = sb_mma16<2>(fq[buf][u], bfr, aq);
-                    ak = sb_mma16<2>(fk[buf][u], bfr, ak);
-                    av = sb_mma16<2>(fv[buf][u], bfr, av);
-                }
-            };
-            fetch(0, 0);
-            for (int ks = 0; ks < nks; ks += 2 * U) {
-                if (ks + U < nks) fetch(1, ks + U);
-                compute(0, ks);
-                if (ks + 2 * U < nks) fetch(0, ks + 2 * U);
-                if (ks + U < nks) compute(1, ks + U);
-            }
-            sb_guard_flush(gm, a.ovf);
-            const float us = a.wqkv_unscale[0];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { aq[r] *= us; ak[r] *= us; av[r] *= us; }
-        }
-        if (!SPLIT && any) {
+        if (any) {
             // two register buffers of U channel groups (literal indices only): the next batch of operand fragments is in flight
             // during the MFMAs of the current one -- a workgroup has the CU almost to itself, nobody else covers an L2 round trip
             constexpr int U = 4;
@@ -972,8 +734,6 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
             for (int r = 0; r < 4; ++r) KL[((u >> 4) * HD + r * 4 + g4) * 16 + (u & 15)] = kq[r];
             *reinterpret_cast<wf4*>(VL + u * HD + g4 * 4) = wf4{vq[0], vq[1], vq[2], vq[3]};
         }
-    } else {
-        qv = *reinterpret_cast<const wf4*>(a.q + b * a.q_bs + (long)max(qpix, 0) * a.q_ld + c0 + 4 * g4);
     }
     if (qpix < 0) qv = wf4{0.f, 0.f, 0.f, 0.f};
     const float* bias = a.biasT + (long)head * nkey * ATT_TOK + min(qi, ATT_TOK - 1);
@@ -994,7 +754,7 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
             const int u = it >> 2, cg = it & 3;
             const int d = min(u / ATT_TOK, a.D - 1), tok = u - (u / ATT_TOK) * ATT_TOK;
             const int pix = u < nkey ? token_pixel(tok) : -1;
-            const float* kp = (u < nkey && !(FUSE && d == a.q_slot)) ? a.kv[d] : nullptr;
+            const float* kp = (u < nkey && d != a.q_slot) ? a.kv[d] : nullptr;
             const bool use = pix >= 0 && kp != nullptr;
             const float* ksrc = use ? kp + b * a.kv_bs[d] + (long)pix * a.kv_ld[d] + a.k_off[d] + c0 + cg * 4 : a.kvpad + c0 + cg * 4;
             const float* vsrc = use ? kp + b * a.kv_bs[d] + (long)pix * a.kv_ld[d] + a.v_off[d] + c0 + cg * 4 : a.kvpad + a.C + c0 + cg * 4;
@@ -1004,7 +764,7 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int it = tid + t * 256;
-            if (it < NT * 16 * 4 && !(FUSE && (it >> 2) / ATT_TOK == a.q_slot)) {     // (fused: the query frame's rows are written above)
+            if (it < NT * 16 * 4 && (it >> 2) / ATT_TOK != a.q_slot) {     // (the query frame's rows are written above)
                 const int u = it >> 2, cg = it & 3;
                 // channel cg*4 + e of the head is contracted at k-step e by the lanes g4 = cg: LDS row e*4 + cg
 #pragma unroll
@@ -1054,9 +814,7 @@ __global__ __launch_bounds__(256) void attn_tok16_kernel(const AttnTokArgs a) {
 
 static int attn_tok16_launch(const AttnTokArgs& a, int B, hipStream_t s) {
     const int nW = (a.Hp / ATT_WS) * (a.Wp / ATT_WS);
-    if (a.x && a.wqkvS && a.C % 32 == 0) hipLaunchKernelGGL((attn_tok16_kernel<true, true>), dim3(nW, a.heads, B), dim3(256), 0, s, a);
-    else if (a.x) hipLaunchKernelGGL((attn_tok16_kernel<true, false>), dim3(nW, a.heads, B), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_tok16_kernel<false, false>), dim3(nW, a.heads, B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(attn_tok16_kernel, dim3(nW, a.heads, B), dim3(256), 0, s, a);
     BDE_HIP(hipGetLastError());
     return BDE_OK;
 }

@@ -249,7 +249,7 @@ def test_long_sequence_more_frames_than_one_pointer_block():
 
 @pytest.mark.parametrize('name', sorted(CFGA_SAMPLED))
 def test_config_a_at_baseline_resolutions(name):
-    """Canonical channel widths / heads / depths (the kernels bench.py times: winblock, attn_mfma16, lstm16<1,128,2>,
+    """Canonical channel widths / heads / depths (the kernels bench.py times: winblock, wide_core, lstm16<1,128,2>,
     every conv_vec tile shape) at every BASELINE.json resolution and at bench.py's T=16, against the REFERENCE's
     outputs (sampled pixels + per-frame mean/std, oracle/gen_golden.py::gen_cfgA_sampled)."""
     z, meta = load_golden(name)
@@ -515,9 +515,9 @@ def test_one_sequence_split_over_two_ranks_by_direction(tmp_path):
         assert v['err'] <= TOL, (name, v['err'])
 
 
-def test_round3_kernels_agree_with_the_kernels_they_replace():
-    """The split-operand recurrent step (lstm_sb.h), the split GEMM phases of the attention block (winblock_sb.h), the q|k|v
-    fusion of the level-2 core (wideblock.h), the two-stream sweep option, the x-part of the gates inside the step, the operand
+def test_switched_kernels_agree_with_the_default_build():
+    """The split-operand recurrent step (lstm_sb.h), the split GEMM phases of the attention block (winblock_sb.h), the fp32
+    chain of the level-2 attention (wideblock.h: wide_kv_sb, wide_fuse_mlp), the two-stream sweep option, the x-part of the gates inside the step, the operand
     format (two fp16 terms vs three bf16 terms) and the split convolutions altogether: each switched in turn must give the
     frames of the default build to fp32 rounding (canonical config, 184x240, T = 6) -- and all of them match the reference's
     golden frames through the other tests."""
@@ -533,8 +533,8 @@ def test_round3_kernels_agree_with_the_kernels_they_replace():
         base = torch.stack(m(inp)).clone()
         assert [m.get_info(f'sb_lstm{l}') for l in range(3)] == [1, 1, 1]
         terms = m.get_info('sb_terms')                                 # 2 unless BDE_SB_TERMS says otherwise
-        for key, off, on in (('lstm_sbk', 0, 1), ('winblock_sb', 0, 1), ('wide_fuse_qkv', 0, 1), ('lstm_two_streams', 1, 0),
-                             ('lstm_fuse_x', 0, 1), ('sb_terms', 5 - terms, terms), ('conv_sb', 0, 1), ('wide_kv_sb', 0, 1), ('wide_fuse_mlp', 0, 1), ('wide_fuse_fc2', 0, 1), ('wide_core2', 0, 1), ('wide_spl', 0, 1), ('head3', 0, 1)):
+        for key, off, on in (('lstm_sbk', 0, 1), ('winblock_sb', 0, 1), ('lstm_two_streams', 1, 0),
+                             ('lstm_fuse_x', 0, 1), ('sb_terms', 5 - terms, terms), ('conv_sb', 0, 1), ('wide_kv_sb', 0, 1), ('wide_fuse_mlp', 0, 1), ('head3', 0, 1)):
             m.set_tuning(key, off)
             try:
                 y = torch.stack(m(inp))

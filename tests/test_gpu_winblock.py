@@ -99,9 +99,9 @@ def test_inputs_untouched_and_deterministic(model_a):
 
 
 @pytest.mark.parametrize('shape', [(1, 256, 7, 9), (2, 256, 23, 30), (1, 256, 15, 16)])
-def test_level2_matrix_core_attention_vs_oracle(model_a, shape):
-    """Head dim 16 (level 2 of config A): attention core on the matrix cores (csrc/attn_mfma.h) against the
-    oracle and against the vector-ALU core (csrc/attn.h)."""
+def test_level2_split_chain_vs_fp32_chain_and_oracle(model_a, shape):
+    """Head dim 16 (level 2 of config A): the split chain (csrc/wide_core.h + wide_mlp.h, two-term operands) against the
+    oracle and against the fp32 chain (csrc/wideblock.h: attn_tok16_kernel + tokgemm_kernel)."""
     from bde2vid_amd import ops
     cfg, sd, m = model_a
     bufs = [torch.from_numpy(dense_like(shape, 380 + d)) for d in range(3)]
@@ -109,12 +109,14 @@ def test_level2_matrix_core_attention_vs_oracle(model_a, shape):
     ref = oracle_blocks(cfg, sd, bufs, 0, 2, level=2)
     y = ops.dframe_attention(m, 2, dev, 0, 2)
     assert maxabs(y, ref) <= TOL
-    m.set_tuning('attn_mfma', 0)
+    m.set_tuning('wide_kv_sb', 0)
+    m.set_tuning('wide_fuse_mlp', 0)
     try:
-        y_valu = ops.dframe_attention(m, 2, dev, 0, 2)
+        y_fp32 = ops.dframe_attention(m, 2, dev, 0, 2)
     finally:
-        m.set_tuning('attn_mfma', 1)
-    assert maxabs(y, y_valu.cpu()) <= TOL
+        m.set_tuning('wide_kv_sb', 1)
+        m.set_tuning('wide_fuse_mlp', 1)
+    assert maxabs(y, y_fp32.cpu()) <= TOL
     ref0 = oracle_blocks(cfg, sd, [None, bufs[1], None], 0, 2, level=2)
     assert maxabs(ops.dframe_attention(m, 2, [None, dev[1], None], 0, 2), ref0) <= TOL
 

@@ -21,7 +21,7 @@ SPAN_KERNELS = [
     ('wide_*(tokgemm)', r'tokgemm_kernel'),
     ('wide_core2', r'wide_core_kernel|attn_tok16_kernel'),
     ('wide_mlp2', r'mlp_fused_kernel'),
-    ('wide_kv_all2', r'tokgemm_sb_kernel'),
+    ('wide_kv_all2', r'tokgemm_sb_rows_kernel|tokgemm_sb_kernel'),
     ('lstm0', r'lstm_sb_step_kernel<4, 1, 2|lstm16_step_kernel<1, 128, 2'),
     ('lstm1', r'lstm_sb_step_kernel<2, 2, 2|lstm16_step_kernel<1, 64, 1'),
     ('lstm2', r'lstm_sb_step_kernel<1, 4, 3|lstm16_step_kernel<2, 32, 1'),
@@ -31,7 +31,6 @@ SPAN_KERNELS = [
     ('dec_conv*+head', r'conv_sb_kernel<5, 1|conv_vec_kernel<5, 1'),
     ('gates_x2(dword path)', r'conv_mfma_kernel<3, 1'),
     ('chain(pw_gemm)', r'pw_gemm_kernel'),
-    ('chain_core2', r'attn_mfma16_kernel'),
     ('dec_up*', r'upsample2x_sum_kernel'),
     ('pred', r'pred_kernel'),
     ('merge*', r'add2_kernel'),
